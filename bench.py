@@ -59,6 +59,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-host-boundary", action="store_true", help="N = 1: skip config.host_boundary and the per-frame calls (profiling runs: their launches would mix into the per-kernel figures of the HBM-resident step)")
     ap.add_argument("--rehearse-one-gpu", action="store_true", help="N > 1 on a one-GPU box: every rank on GPU 0, collectives over gloo on CPU tensors (rehearses the multi-rank path with the real codecs; not a scaling measurement)")
     ap.add_argument("--selftest-launcher", action="store_true", help="no codec, no GPU: ranks exchange synthetic packets over gloo (tests the launcher, the sharding and the gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one handed its caller (packets, "
+                    "their sizes and frame types, the decoded frames; per-frame byte sums whole, the bytes as a fixed seeded sample) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -388,7 +390,45 @@ def measure(runner, wl, frames, steps, warmup, barrier=None, seed=None, after=No
         tor.cuda.synchronize(runner.dev)
     elapsed = time.perf_counter() - t0
     assert runner.same(dec, frames), "the decoded frames differ from the input: the round trip is not lossless"
-    return dict(out=out, sizes=sizes, ft=ft, elapsed=elapsed, t_enc=te / steps, t_dec=td / steps, samples=samples, stage_ms={k: v / steps for k, v in acc.items()})
+    return dict(out=out, sizes=sizes, ft=ft, dec=dec, elapsed=elapsed, t_enc=te / steps, t_dec=td / steps, samples=samples, stage_ms={k: v / steps for k, v in acc.items()})
+
+
+DUMP_SAMPLE = 1 << 22  # bytes sampled from the packets and from the decoded frames: 2 x 16 MB of float32
+
+
+def _sample_index(n, seed):
+    """a fixed, seeded, sorted sample of positions in [0, n): all of them when n is small"""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(d, m, prefix=""):
+    """--dump-outputs: what the last timed step gave its caller, as float32 / float64 .npy files under d (at most ~33 MB).
+    The packets (one byte stream, frame after frame) and the decoded frames are too big to keep whole: every frame's byte sum is
+    kept exactly, the bytes themselves as a sample at fixed seeded positions (the decoded frames' positions depend on the
+    geometry alone, the packets' on the stream's length too)."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    sizes = np.asarray(m["sizes"], dtype=np.int64)
+    n = sizes.size
+    packets = m["out"].reshape(-1)
+    offs = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)])).to(packets.device)
+    csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=packets.device), packets.to(torch.int64).cumsum(0)])
+    dec = m["dec"].reshape(n, -1)
+    arrays = {
+        "packet_sizes": sizes.astype(np.float64),
+        "frame_types": np.asarray(m["ft"], dtype=np.float64),
+        "packet_byte_sums": (csum[offs[1:]] - csum[offs[:-1]]).cpu().numpy().astype(np.float64),
+        "packet_bytes_sample": packets[torch.from_numpy(_sample_index(packets.numel(), 1)).to(packets.device)].cpu().numpy().astype(np.float32),
+        "decoded_frame_byte_sums": dec.sum(1, dtype=torch.int64).cpu().numpy().astype(np.float64),
+        "decoded_bytes_sample": dec.reshape(-1)[torch.from_numpy(_sample_index(dec.numel(), 2)).to(dec.device)].cpu().numpy().astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(d, prefix + name + ".npy"), a)
+    return sorted(arrays)
 
 
 def golden_stream(name):
@@ -693,6 +733,9 @@ def run_rank(args):
             gathered["p"], gathered["s"] = gather_packets_end(gathered.pop("h"))
 
     m = measure(runner, wl, frames, args.steps, args.warmup, barrier, seed, (exchange_begin, exchange_end))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m, "" if world == 1 else f"rank{rank}_")
+    m.pop("dec")  # (a view of the runner's buffer: not kept alive past the runner)
     if seed is not None and seed.error:
         raise RuntimeError("motion pre-pass: " + seed.error)
     tmax = torch.tensor([m["elapsed"]], device=cdev, dtype=torch.float64)

@@ -1,9 +1,11 @@
 """CPU tests of the ORACLE (oracle/): the rANS arithmetic pinned against the
-reference's own rans_byte.h (oracle/_ref, built in place where the reference
-tree exists), the two known answers SURVEY.md §8c records from the real
+reference's own rans_byte.h (its answers stored in golden/ref_rans.json, and
+oracle/_ref itself where it was built from the reference tree), the two known answers SURVEY.md §8c records from the real
 reference, and lossless round trips over the edge cases the format has."""
 import ctypes as C
 import hashlib
+import importlib.util
+import json
 import os
 
 import numpy as np
@@ -12,75 +14,78 @@ import pytest
 import oracle_api as O
 from screenpressor_amd.synth import DesktopSequence, pack24
 
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_spec = importlib.util.spec_from_file_location("make_ref_rans", os.path.join(GOLD, "make_ref_rans.py"))
+R = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(R)
+REF_RANS = json.load(open(os.path.join(GOLD, "ref_rans.json")))  # the reference's answers to the cases below (make_ref_rans.py)
 REF_SO = os.path.join(O.ORACLE_DIR, "_ref", "librefrans.so")
 
 
-def _random_entries(rng, n, raw_frac=0.1):
-    """valid coder entries: (freq, cum) with cum+freq <= 4096, some raw bytes"""
-    freq = rng.integers(1, 4097, n)
-    # skew towards small and large frequencies
-    freq = np.where(rng.random(n) < 0.3, rng.integers(1, 8, n), freq)
-    cum = (rng.random(n) * (4096 - freq + 1)).astype(np.int64)
-    e = np.stack([freq, cum], axis=1).astype(np.uint16)
-    raw = rng.random(n) < raw_frac
-    e[raw, 0] = 0
-    e[raw, 1] = rng.integers(0, 256, raw.sum())
-    return e
+def _rans_decode_values(data, e):
+    """the byte-wise rANS decoder (32-bit state, lower bound 2^23, 12-bit probabilities) over `data`: (bytes used, the 12-bit
+    value or raw byte taken per entry)"""
+    buf = data + b"\0" * 8
+    x, p = int.from_bytes(buf[:4], "little"), 4
+    vals = np.zeros(len(e), dtype=np.uint16)
+    for i, (freq, cum) in enumerate(e.tolist()):
+        if freq:
+            vals[i] = x & 4095
+            x = freq * (x >> 12) + (x & 4095) - cum
+            while x < 1 << 23:
+                x, p = (x << 8) | buf[p], p + 1
+        else:
+            vals[i], p = buf[p], p + 1
+    return p, vals
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (no reference tree and no prebuilt copy)")
-@pytest.mark.parametrize("n", [1, 2, 17, 1000, 131072])
+@pytest.mark.parametrize("n", R.BLOCK_NS)
 def test_rans_block_matches_reference_header(n):
-    """oracle rANS restatement == reference rans_byte.h driven as ransmt.h:116-134 does"""
-    ref = C.CDLL(REF_SO)
-    rng = np.random.default_rng(n)
-    e = _random_entries(rng, n)
+    """oracle rANS restatement == reference rans_byte.h driven as ransmt.h:116-134 does (its bytes as stored in
+    golden/ref_rans.json, and live where oracle/_ref is built)"""
+    want = REF_RANS["blocks"][str(n)]
+    e = R.block_entries(n)
     mine = O.rans_block(e)
-    out = np.zeros(2 * n + 16, dtype=np.uint8)
-    scratch = np.zeros(2 * n + 16, dtype=np.uint8)
-    sz = ref.ref_rans_block(e.ctypes.data_as(C.c_void_p), n, out.ctypes.data_as(C.c_void_p),
-                            scratch.ctypes.data_as(C.c_void_p), scratch.size)
-    assert bytes(out[:sz]) == mine
-    # and the reference decoder walks those bytes back through every interval
-    vals = np.zeros(n, dtype=np.uint16)
-    buf = np.frombuffer(mine + b"\0" * 8, dtype=np.uint8)
-    used = ref.ref_rans_decode_values(buf.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), n,
-                                      vals.ctypes.data_as(C.c_void_p))
+    assert (len(mine), R.sha256(mine)) == (want["bytes"], want["sha256"])
+    # and the decoder walks those bytes back through every interval, taking what the reference decoder took
+    used, vals = _rans_decode_values(mine, e)
+    assert (used, R.sha256(vals.astype("<u2").tobytes())) == (want["used"], want["values_sha256"])
     assert used == len(mine)
     coded = e[:, 0] > 0
     assert np.all(vals[coded] >= e[coded, 1]) and np.all(vals[coded] < e[coded, 1].astype(int) + e[coded, 0])
     assert np.array_equal(vals[~coded], e[~coded, 1])
+    if os.path.exists(REF_SO):
+        ref = R.Ref(REF_SO)
+        assert ref.block(e) == mine
+        rused, rvals = ref.decode_values(mine, e)
+        assert rused == used and np.array_equal(rvals, vals)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (no reference tree and no prebuilt copy)")
 def test_product_rans_algebra_is_the_reference_headers_symbol_form():
-    """rans_byte.h:171-241, :255-278 (RansEncSymbolInit / RansEncPutSymbol, compiled in place) against the table and the step the
+    """rans_byte.h:171-241, :255-278 (RansEncSymbolInit / RansEncPutSymbol) against the table and the step the
     product's rANS kernels implement (csrc/scpr_model.hpp rans_rcp; k_rans / k_rans_s): for EVERY freq 1..4096 the reciprocal,
     the shift, bias - start, x_max and 4096 - freq are the header's, and one step from a spread of states and starts gives the
-    header's new state and bytes.  (The kernels themselves are compared with the oracle on the GPU; this moves their arithmetic
-    from "equals the oracle, which equals the header's other form" to "equals the header".)"""
+    header's new state and bytes - the header's answers as stored in golden/ref_rans.json, and live where oracle/_ref is built.
+    (The kernels themselves are compared with the oracle on the GPU; this moves their arithmetic from "equals the oracle, which
+    equals the header's other form" to "equals the header".)"""
     from screenpressor_amd import build as B
     hm = C.CDLL(B.build_host_harness())
-    ref = C.CDLL(REF_SO)
-    ref.ref_enc_put_symbol.restype = C.c_uint32
     hm.hm_rans_step.restype = C.c_uint32
-    rng = np.random.default_rng(7)
-    r5, h3 = (C.c_uint32 * 5)(), (C.c_uint32 * 3)()
-    rb, hb = (C.c_uint8 * 8)(), (C.c_uint8 * 8)()
-    rn, hn = C.c_int(), C.c_int()
-    edge_states = [1 << 23, (1 << 23) + 1, (1 << 31) - 1, (1 << 31) - 256, 1 << 30, (1 << 27) - 1, 1 << 27]
-    for freq in range(1, 4097):
+    h3, hb, hn = (C.c_uint32 * 3)(), (C.c_uint8 * 8)(), C.c_int()
+
+    def params(freq, start):
         hm.hm_rans_params(freq, h3)
-        for start in {0, 4096 - freq, int(rng.integers(0, 4096 - freq + 1))}:
-            ref.ref_enc_symbol_init(start, freq, r5)
-            x_max, rcp, bias, cmpl, shift = list(r5)
-            assert (x_max, rcp, shift, bias - start, cmpl) == ((freq << 19) & 0xFFFFFFFF, h3[0], h3[1], h3[2], 4096 - freq), (freq, start)
-            states = edge_states + [(freq << 19) - 1, freq << 19, min((freq << 27) - 1, (1 << 31) - 1), min(freq << 27, (1 << 31) - 1)] + rng.integers(1 << 23, 1 << 31, 6).tolist()
-            for x in states:
-                x = int(max(1 << 23, min(x, (1 << 31) - 1)))
-                a = ref.ref_enc_put_symbol(x, start, freq, rb, C.byref(rn))
-                b = hm.hm_rans_step(x, start, freq, hb, C.byref(hn))
-                assert (a, rn.value, bytes(rb[:rn.value])) == (b, hn.value, bytes(hb[:hn.value])), (freq, start, x)
+        return (freq << 19) & 0xFFFFFFFF, h3[0], h3[1], h3[2], 4096 - freq
+
+    def step(x, start, freq):
+        s = hm.hm_rans_step(x, start, freq, hb, C.byref(hn))
+        return (s, hn.value) + tuple(hb[:hn.value])
+    mine = list(R.algebra_records(params, step))
+    if os.path.exists(REF_SO):
+        ref = R.Ref(REF_SO)
+        for (freq, start, x), r in mine:
+            assert (ref.params(freq, start) if x is None else ref.step(x, start, freq)) == r, (freq, start, x)
+    assert (len(mine), R.digest(mine)) == (REF_RANS["algebra"]["records"], REF_RANS["algebra"]["sha256"])
 
 
 def test_survey_known_answers():
