@@ -113,6 +113,36 @@ int64_t scpr_compress_batch(scpr_codec* c, const void* d_frames, int nframes, in
 int scpr_decompress_batch(scpr_codec* c, const void* d_packets, const uint32_t* sizes, const int* ftypes,
                           int nframes, void* d_frames_out, int pitch);
 
+/* ---- many streams in one launch (an addition) -------------------------------
+ * One entry per codec: the arguments of scpr_decompress_batch, and its result. */
+typedef struct scpr_decode_call {
+    scpr_codec* codec;
+    const void* d_packets;   /* device memory, as scpr_decompress_batch */
+    const uint32_t* sizes;   /* host */
+    const int* ftypes;       /* host */
+    int nframes;
+    void* d_frames_out;      /* device memory */
+    int pitch;
+    int result;              /* out: what scpr_decompress_batch(codec, ...) would have returned */
+} scpr_decode_call;
+
+/* Decodes the entries' streams with their GOPs side by side in shared launches (a GOP is one dependent chain on one wave: a
+ * single stream leaves most of the GPU idle, many streams fill it).
+ * Contract: observably the same as calling scpr_decompress_batch on every entry in turn - each entry's `result` (frames done,
+ * SCPR_E_STREAM, SCPR_E_DEVICE, ...), the pictures written, and the state every codec is left in (the next call on it, of
+ * either kind, continues exactly as it would have).  One entry's failure does not stop the others.  Returns once everything
+ * it wrote is complete.
+ * Returns SCPR_E_PARAM and touches nothing (no codec, no `result`) when `calls` is NULL or ncalls < 0, a codec is NULL or not
+ * initialised, the same codec appears twice, the codecs are on different devices, or an entry has a NULL pointer or
+ * nframes < 0.  ncalls == 0 is SCPR_OK.  Otherwise SCPR_OK, with the outcomes in `result`; SCPR_E_DEVICE only when a launch
+ * itself failed (its entries' `result` say SCPR_E_DEVICE too).
+ * Version 2 (range-coder) streams are decoded inside the call by the codec's own path, with the same `result`.
+ * The launches run on the stream of the first entry's codec; every codec's own stream is waited for before them.
+ * Timing: scpr_last_timing of every codec whose stream went through the shared launches reports the WHOLE call - "decode" is
+ * the summed time of the call's launches, "unpack" the summed time of every codec's unpack kernels.  A version 2 entry's codec
+ * reports its own decode. */
+int scpr_decompress_streams(scpr_decode_call* calls, int ncalls);
+
 /* ---- batch entry points with HOST pointers (an addition) --------------------
  * The reference's boundary hands over host memory (ScreenCodec::CompressFrame,
  * screencap.cpp:1632: pSrc / pDst; DecompressFrame, :1695).  These are the two

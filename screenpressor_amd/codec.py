@@ -17,7 +17,7 @@ _LIB_PATH = os.environ.get("SCPR_AMD_LIB", os.path.join(_PKG, "libscpr_amd.so"))
 
 SCPR_OK, SCPR_E_DEVICE, SCPR_E_PARAM, SCPR_E_BAD_VERSION, SCPR_E_CAPACITY, SCPR_E_STREAM = 0, -1, -2, -3, -4, -5
 EXPORTS = ["scpr_create", "scpr_destroy", "scpr_init", "scpr_deinit", "scpr_crash_happened", "scpr_compress_frame",
-           "scpr_decompress_frame", "scpr_compress_batch", "scpr_decompress_batch", "scpr_compress_batch_host", "scpr_decompress_batch_host", "scpr_host_pin", "scpr_host_unpin", "scpr_last_timing", "scpr_stage_name",
+           "scpr_decompress_frame", "scpr_compress_batch", "scpr_decompress_batch", "scpr_decompress_streams", "scpr_compress_batch_host", "scpr_decompress_batch_host", "scpr_host_pin", "scpr_host_unpin", "scpr_last_timing", "scpr_stage_name",
            "scpr_seed_shard", "scpr_export_mv_memory", "scpr_import_mv_memory", "scpr_motion_prepass", "scpr_debug_entries", "scpr_debug_arena", "scpr_debug_colour_chain", "scpr_debug_inject", "scpr_debug_rans_recoded", "scpr_version",
            # include/scpr_driver.h, include/scpr_avi.h
            "scpr_driver_open", "scpr_driver_close", "scpr_driver_configure", "scpr_driver_compress_query", "scpr_driver_compress_get_format",
@@ -31,6 +31,12 @@ class ScprParams(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in (
         "width", "height", "bits_per_pixel", "red_mask", "green_mask", "blue_mask",
         "high_range_x", "high_range_y", "low_range_x", "low_range_y", "loss", "workers")]
+
+
+class ScprDecodeCall(C.Structure):
+    """scpr_decode_call (include/scpr_amd.h)"""
+    _fields_ = [("codec", C.c_void_p), ("d_packets", C.c_void_p), ("sizes", C.POINTER(C.c_uint32)), ("ftypes", C.POINTER(C.c_int)),
+                ("nframes", C.c_int), ("d_frames_out", C.c_void_p), ("pitch", C.c_int), ("result", C.c_int)]
 
 
 class BadVersionException(Exception):
@@ -65,6 +71,7 @@ def load_library() -> C.CDLL:
         L.scpr_compress_batch.restype = C.c_int64
         L.scpr_compress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.scpr_decompress_batch.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int]
+        L.scpr_decompress_streams.argtypes = [C.POINTER(ScprDecodeCall), C.c_int]
         L.scpr_compress_batch_host.restype = C.c_int64
         L.scpr_compress_batch_host.argtypes = L.scpr_compress_batch.argtypes
         L.scpr_decompress_batch_host.argtypes = L.scpr_decompress_batch.argtypes
@@ -310,6 +317,46 @@ class ScreenCodec:
         if n > 0:
             self._L.scpr_debug_entries(self._h, out.ctypes.data_as(C.c_void_p), n)
         return out
+
+
+def decompress_streams(calls, sync: bool = True):
+    """scpr_decompress_streams: many codecs' streams decoded with their GOPs side by side in shared launches.
+
+    calls: a list of (codec, packets, sizes, ftypes[, pitch[, out]]) with torch device tensors, as ScreenCodec.DecompressBatch
+    takes them (pitch None: the codec's DIB pitch; out None: allocated).  Returns a list of (result, out) in the same order:
+    result is what DecompressBatch's C call would have returned for that codec - frames decoded, or a negative error code, which
+    is returned here rather than raised so that one bad stream does not hide the others.  A refusal of the whole call
+    (SCPR_E_PARAM: a codec twice, an uninitialised codec, ...) raises, and then no codec has been touched.
+    sync=False: the caller vouches that the packets are complete (see ScreenCodec.CompressBatch)."""
+    import torch
+    L = load_library()
+    n = len(calls)
+    arr = (ScprDecodeCall * max(n, 1))()
+    keep, outs = [], []
+    dev = None
+    for i, call in enumerate(calls):
+        codec, packets, sizes, ftypes = call[:4]
+        height = getattr(codec, "height", 0)  # (a codec never initialised is refused by the C side)
+        pitch = call[4] if len(call) > 4 and call[4] is not None else getattr(codec, "pitch", 0)
+        out = call[5] if len(call) > 5 else None
+        k = len(sizes)
+        assert len(ftypes) == k
+        assert packets.is_cuda and packets.dtype == torch.uint8 and packets.numel() >= int(np.sum(sizes, dtype=np.uint64))
+        if out is None:
+            out = torch.empty(max(k * pitch * height, 1), dtype=torch.uint8, device=packets.device)
+        assert out.is_cuda and out.numel() >= k * pitch * height
+        sz = (C.c_uint32 * max(k, 1))(*[int(x) for x in sizes])
+        ft = (C.c_int * max(k, 1))(*[int(x) for x in ftypes])
+        keep += [sz, ft]
+        arr[i] = ScprDecodeCall(codec._h, packets.data_ptr(), sz, ft, k, out.data_ptr(), pitch, 0)
+        outs.append(out)
+        dev = packets.device
+    if sync and dev is not None:
+        torch.cuda.synchronize(dev)
+    rc = L.scpr_decompress_streams(arr, n)
+    if rc != SCPR_E_DEVICE:  # (a failed launch: its entries say so in their results)
+        ScreenCodec._check(rc)
+    return [(arr[i].result, outs[i]) for i in range(n)]
 
 
 def debug_colour_chain(syms, f0: int = 32, device: int = 0) -> np.ndarray:

@@ -175,6 +175,8 @@ struct scpr_codec {
   hipStream_t stream3 = nullptr;
   hipEvent_t ev_in[2] = {nullptr, nullptr};
   DevBuf hb_frames, hb_packets, hb_list;
+  // scpr_decompress_streams, on the codec of its first entry: the launch's stream descriptors, GOP list and status read-back
+  DevBuf ms_streams, ms_refs, ms_status;
   struct HostRange {
     void* base;
     size_t bytes;
@@ -1008,7 +1010,7 @@ void scpr_destroy(scpr_codec* c) {
     (void)hipStreamDestroy(c->stream3);
     for (int k = 0; k < 2; k++) (void)hipEventDestroy(c->ev_in[k]);
   }
-  DevBuf* all[] = {&c->hb_frames, &c->hb_packets, &c->hb_list, &c->snap_mvs, &c->snap_state, &c->planes, &c->tnmap, &c->exitmap, &c->entry, &c->runrec, &c->tilecnt, &c->tileoff, &c->hdrrec, &c->hdrcnt, &c->frametot, &c->flags, &c->slotlist, &c->genlist,
+  DevBuf* all[] = {&c->hb_frames, &c->hb_packets, &c->hb_list, &c->ms_streams, &c->ms_refs, &c->ms_status, &c->snap_mvs, &c->snap_state, &c->planes, &c->tnmap, &c->exitmap, &c->entry, &c->runrec, &c->tilecnt, &c->tileoff, &c->hdrrec, &c->hdrcnt, &c->frametot, &c->flags, &c->slotlist, &c->genlist,
                    &c->bases, &c->totals, &c->runs, &c->runpos, &c->keys[0], &c->keys[1], &c->vals[0], &c->vals[1], &c->cstart, &c->csblocks, &c->cssegs, &c->cscnt, &c->csoff,
                    &c->entries, &c->ranges, &c->rblocks, &c->rscratch, &c->rrec, &c->rsize, &c->packets, &c->pktoff, &c->blkdst, &c->outsizes, &c->total64, &c->arena,
                    &c->arena_top, &c->err, &c->rcp, &c->decframes, &c->decstates, &c->hoststage_in, &c->hoststage_out, &c->chainlists, &c->chaincounts, &c->fixr.cnt, &c->fixr.off, &c->fixr.tot, &c->fixr.sym, &c->fixr.pos, &c->fixr.gen, &c->fixm.cnt, &c->fixm.off, &c->fixm.tot, &c->fixm.sym, &c->fixm.pos, &c->fixm.gen, &c->kinds, &c->pidx, &c->fidx, &c->pframes, &c->pflag, &c->binfo, &c->smv, &c->btype, &c->bmv, &c->bcnt, &c->boff, &c->bflag, &c->plist, &c->pinfo, &c->ptot, &c->pbase, &c->misc, &c->miscpos, &c->miscranges, &c->mvs, &c->mvs_keep, &c->fixed_persist, &c->misc_persist, &c->colour_persist, &c->decgops, &c->decfixed, &c->dec_fixed_persist, &c->dec_colour_persist, &c->dec_arena, &c->dec_arena2, &c->arena2, &c->dec_arena_top, &c->mvdict, &c->mvpre, &c->gmask};
@@ -1486,281 +1488,387 @@ int64_t scpr_compress_batch(scpr_codec* c, const void* d_frames, int nframes, in
   return r < 0 ? enc_failed(c, txn, ftypes, r) : r;
 }
 
+// ---- decompression in three steps per chunk: preparation (head parse, lists, arena), launch, epilogue (error word, kept state,
+// unpack).  decompress_core takes one codec through them with a launch of its own; scpr_decompress_streams takes many codecs
+// through the same steps with their GOPs in one launch.
+struct DecCall {  // one codec's call: its arguments, its progress, and the chunk in hand
+  scpr_codec* c = nullptr;
+  const u8* pk = nullptr;
+  const uint32_t* sizes = nullptr;
+  const int* ftypes = nullptr;
+  int nframes = 0;
+  u8* out = nullptr;
+  int pitch = 0;
+  bool out_is_host = false;
+  std::vector<u64> offs;  // packet offsets
+  std::vector<u32> heads; // first bytes of every packet
+  int f0 = 0, done = 0;
+  // the chunk: frames f0 .. f0 + n, the host state it starts from (restored for every attempt), the lists of the attempt
+  int n = 0, attempt = 0;
+  bool host_crashed = false, host_flat = false;
+  u32 host_flat_rgb = 0, host_frames_done = 0;
+  std::vector<DecFrame> fr;
+  std::vector<DecGop> gops;
+  u64 gop_bytes = 0;
+  size_t ng = 0, arena_cap = 0;
+  bool has_p = false, rows_by_streamer = false, streamed_rgb24 = false;
+  int ring = 0, nblocks = 0;
+  u32 errv[8] = {0};
+  u32 atop = 0;
+};
+// results of the steps besides SCPR_OK and the errors: the call ends with the frames done so far / the chunk is decoded again
+enum { DEC_STOP = 1, DEC_AGAIN = 2 };
+
+// first bytes of every packet decide version / flat / coded (screencap.cpp:1700, :1536); queued on the codec's stream, delivered
+// by its next sync_out
+static int dec_heads(DecCall& d) {
+  scpr_codec* c = d.c;
+  hipStream_t st = c->stream;
+  d.offs.assign((size_t)d.nframes + 1, 0);
+  for (int i = 0; i < d.nframes; i++) d.offs[i + 1] = d.offs[i] + d.sizes[i];
+  d.heads.assign((size_t)d.nframes, 0);
+  if (d.nframes) {
+    HIPCHK(c->pktoff.reserve((size_t)(d.nframes + 1) * 8));
+    HIPCHK(c->outsizes.reserve((size_t)d.nframes * 4));
+    HIPCHK(h2d(c, c->pktoff.p, d.offs.data(), (size_t)(d.nframes + 1) * 8, st));
+    hipLaunchKernelGGL(k_heads, dim3((d.nframes + 255) / 256), dim3(256), 0, st, d.pk, c->pktoff.as<u64>(), d.nframes, c->outsizes.as<u32>());
+    HIPCHK(d2h(c, d.heads.data(), c->outsizes.p, (size_t)d.nframes * 4, st));
+  }
+  return SCPR_OK;
+}
+
+// step 1a: the next chunk's frames (d.f0 < d.nframes)
+static int dec_chunk_open(DecCall& d) {
+  scpr_codec* c = d.c;
+  const int f0 = d.f0;
+  if (!c->have_codec) {
+    if (d.ftypes[f0] > 0) return DEC_STOP;  // P-frame before any key frame (:1699)
+    int version = (int)((d.heads[f0] & 0xFF) >> 4) + 1;
+    int rc = ensure_codec(c, version);
+    if (rc != SCPR_OK) return rc;
+  }
+  // a chunk: as many frames as there are planes for, and no more GOPs than the GPU runs side by side (768 chains)
+  int n = 0;
+  for (int keys = 0; f0 + n < d.nframes && n < c->dslots; n++)
+    if (d.ftypes[f0 + n] == 0 && ++keys > 768) break;
+  {
+    int rc = ensure_planes(c, (size_t)n);
+    if (rc != SCPR_OK) return rc;
+  }
+  // A chunk of fresh GOPs is decoded with a dense-table arena sized from its packets (a table per 12 bytes of stream, below);
+  // should that not be enough the device reports an overflow (nothing is lost: the contexts past the end share the sink
+  // table) and the chunk is decoded again with the true bound (every context of every GOP dense, 12288 tables per GOP).
+  d.n = n;
+  d.attempt = 0;
+  d.host_crashed = c->crashed, d.host_flat = c->last_flat;
+  d.host_flat_rgb = c->last_flat_rgb, d.host_frames_done = c->frames_done;
+  return SCPR_OK;
+}
+
+// step 1b: one attempt's lists, records and arena, on the codec's stream.  own_launch: the chunk gets a launch of its own
+// (decompress_core: its decode stage is timed here, and its key frames may leave through the row streamer)
+static int dec_chunk_prepare(DecCall& d, bool own_launch) {
+  scpr_codec* c = d.c;
+  hipStream_t st = c->stream;
+  const Geom& g = c->g;
+  const int f0 = d.f0, n = d.n;
+  // SCPR_DEV_STREAMER=0: the device-resident output never goes through the row streamer (A/B timing; see rows_by_streamer below)
+  static const bool dev_streamer = !(getenv("SCPR_DEV_STREAMER") && atoi(getenv("SCPR_DEV_STREAMER")) == 0);
+  c->crashed = d.host_crashed, c->last_flat = d.host_flat, c->last_flat_rgb = d.host_flat_rgb, c->frames_done = d.host_frames_done;
+  std::vector<DecFrame>& fr = d.fr;
+  std::vector<DecGop>& gops = d.gops;
+  fr.clear();
+  gops.clear();
+  memset(d.errv, 0, sizeof(d.errv));
+  d.atop = 0;
+  HIPCHK(hipMemsetAsync(c->err.p, 0, 32, st));
+  if (own_launch) stage_begin(c, ST_DECODE);
+  u64 gop_bytes = 0;
+  for (int i = 0; i < n; i++) {
+    const int fi = f0 + i;
+    if (c->crashed && d.ftypes[fi] > 0) return DEC_STOP;  // (:1697)
+    c->crashed = false;
+    c->frames_done++;
+    DecFrame df{d.offs[fi], d.sizes[fi], i, 0, i > 0 ? i - 1 : c->pslot};
+    bool new_gop = false;
+    if (d.ftypes[fi]) {  // DecompressP
+      df.kind = 2;
+      c->last_flat = false;
+      if (gops.empty()) gops.push_back({(int)fr.size(), 0, c->dec_live ? 1 : 0, 0});
+    } else if ((d.heads[fi] & 15) == 1) {  // flat key frame (:1537-1553)
+      const u32 rgb = (d.heads[fi] >> 8) & 0xFFFFFFu;
+      df.kind = 1;
+      hipLaunchKernelGGL(k_fill_flat, dim3((g.H * g.S + 255) / 256), dim3(256), 0, st, c->planes.as<u8>(), g, i, rgb);
+      new_gop = !(c->last_flat && c->last_flat_rgb == rgb);  // models renewed unless the colour repeats
+      c->last_flat = true;
+      c->last_flat_rgb = rgb;
+      if (!new_gop && gops.empty()) gops.push_back({(int)fr.size(), 0, c->dec_live ? 1 : 0, 0});
+    } else {
+      df.kind = 0;
+      c->last_flat = false;
+      new_gop = true;
+    }
+    if (new_gop) gops.push_back({(int)fr.size(), 0, 0, 0});
+    fr.push_back(df);
+    gops.back().count++;
+    gop_bytes += d.sizes[fi];
+  }
+  d.gop_bytes = gop_bytes;
+  const size_t ng = d.ng = gops.size();
+  // Key frames of RGB32 output leave through their workgroup's row streamer (a second wave that converts the rows the chain has
+  // finished, scpr_wave.hpp) while the chain runs: always when the pictures go to the host (round 4), and since round 5 also
+  // when they stay on the device, as long as the chunk's workgroups are at most two to a CU - chain and streamer then have a
+  // SIMD each, the decode launch takes what it took (114.9 ms) and k_unpack32's 0.8 ms behind it are gone (headline 133.1 ->
+  // 132.1 ms).  With three workgroups on a CU (more than 512 chains in the chunk) streamers share SIMDs with chains and cost
+  // more than the kernel they spare (2400 key frames: 449.8 ms against 422.9 + 6.1): those chunks are unpacked afterwards.
+  static const size_t dev_streamer_max = getenv("SCPR_DEV_STREAMER_MAX") ? (size_t)atoi(getenv("SCPR_DEV_STREAMER_MAX")) : 512;  // (A/B timing)
+  d.rows_by_streamer = own_launch && (d.out_is_host || (dev_streamer && ng <= dev_streamer_max));
+  d.streamed_rgb24 = false;
+  d.has_p = false;
+  if (!ng) return SCPR_OK;
+  HIPCHK(c->decframes.reserve(fr.size() * sizeof(DecFrame)));
+  HIPCHK(c->decgops.reserve(ng * sizeof(DecGop)));
+  const bool v2 = c->version == 2;  // range-coder streams: count tables instead of context records (scpr_v2.hpp)
+  const size_t state_bytes = v2 ? (size_t)NCOLCTX * V2_COLTAB * 4 : (size_t)NCOLCTX * sizeof(DecRec);
+  const size_t blob_bytes = v2 ? sizeof(V2Fixed) : sizeof(FixedBlob);
+  HIPCHK(c->decstates.reserve(ng * state_bytes));
+  HIPCHK(c->decfixed.reserve(ng * blob_bytes));
+  HIPCHK(c->dec_fixed_persist.reserve(blob_bytes));
+  HIPCHK(c->dec_colour_persist.reserve(state_bytes));
+  if (!v2) HIPCHK(hipMemsetAsync(c->decstates.p, 0, ng * state_bytes, st));  // kind 0 everywhere (RenewI)
+  const bool cont = gops[0].load != 0;
+  if (cont && !v2 && getenv("SCPR_DEBUG_KEYS")) {  // design aid: every table index of the kept records lies inside the kept part of the arena
+    std::vector<u32> hr((size_t)NCOLCTX * DECREC_WORDS);
+    HIPCHK(d2h(c, hr.data(), c->dec_colour_persist.p, hr.size() * 4, st));
+    HIPCHK(sync_out(c, st));
+    size_t bad = 0, dense = 0, firstbad = 0;
+    for (size_t r = 0; r < (size_t)NCOLCTX; r++) {
+      const u32 kind = hr[r * DECREC_WORDS] & 255u;
+      if (kind == 6 || kind == 7) {
+        dense++;
+        if (hr[r * DECREC_WORDS + 2] == 0 || hr[r * DECREC_WORDS + 2] >= c->dec_arena_used) {
+          if (!bad) firstbad = r;
+          bad++;
+        }
+      }
+    }
+    fprintf(stderr, "[scpr debug] continuing GOP: %zu dense records, arena used %zu, bad indices %zu (first record %zu: kind %u index %u)\n", dense, c->dec_arena_used, bad, firstbad,
+            bad ? hr[firstbad * DECREC_WORDS] & 255u : 0u, bad ? hr[firstbad * DECREC_WORDS + 2] : 0u);
+    if (bad) return SCPR_E_DEVICE;
+  }
+  if (cont) {  // the first GOP continues the state kept from the previous call
+    HIPCHK(hipMemcpyAsync(c->decstates.p, c->dec_colour_persist.p, state_bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->decfixed.p, c->dec_fixed_persist.p, blob_bytes, hipMemcpyDeviceToDevice, st));
+  } else {
+    c->dec_arena_used = 1;
+    c->dec_live_bytes = 0;
+  }
+  // Tables alive at the end of this chunk.  The true bound is 12288 per GOP.  In practice a context goes dense once, after at
+  // least 16 of its symbols, each of which cost the stream about a byte or more (raw bytes while nothing repeats, one-slot
+  // intervals of a small table after that: ans_contexts.cpp:3-50; a table per 12 bytes of stream has never been seen
+  // exceeded) - counted over the whole GOP, earlier calls included.  The first attempt of a chunk of fresh GOPs gets that
+  // estimate (round 2 gave it a flat 1024 tables per GOP: a GOP of 300 desktop frames overflowed at frame ~220 and was decoded
+  // twice, 8.2 s instead of 4.2), the second attempt - and a chunk that continues a GOP, which cannot be decoded twice: its
+  // run changes the tables that GOP already owns - the true bound.
+  const size_t true_bound = ng * (size_t)NCOLCTX;
+  size_t estimate = std::min<size_t>(true_bound, (size_t)((c->dec_live_bytes + gop_bytes) / 12) + 8 * ng);
+  if (const char* dbg = getenv("SCPR_DEBUG_DEC_ARENA")) estimate = std::min<size_t>(estimate, (size_t)strtoull(dbg, nullptr, 0));  // (tests reach the second attempt)
+  const size_t budget = v2 ? 0 : (d.attempt || cont) ? true_bound : estimate;
+  // (the arena holds table 0 and the live GOP's tables when a chunk starts: compact_tables after every chunk with several GOPs;
+  // + 1: the sink of an overflow, + slack)
+  const size_t arena_cap = d.arena_cap = std::min<size_t>(1 + true_bound, c->dec_arena_used + budget) + 1 + 64;
+  HIPCHK(c->dec_arena.reserve_keep(arena_cap * sizeof(DenseTab), c->dec_arena_used * sizeof(DenseTab), st));
+  c->h_dec_top0 = (u32)c->dec_arena_used;  // (a member: the source of an asynchronous copy must outlive the call)
+  HIPCHK(h2d(c, c->dec_arena_top.p, &c->h_dec_top0, 4, st));
+  HIPCHK(h2d(c, c->decframes.p, fr.data(), fr.size() * sizeof(DecFrame), st));
+  HIPCHK(h2d(c, c->decgops.p, gops.data(), ng * sizeof(DecGop), st));
+  // LDS ring of 32-bit pixels: the predictors look back one row + 1 pixel, a finished row is flushed at most
+  // one run after it ends, and a run writes up to 255 pixels ahead: a power of two >= W + 512 pixels.
+  // (Keeping static + dynamic LDS under 80 KiB lets two GOPs share a CU.)
+  int ring = 4096;
+  while (ring < 4 * (g.W + 512)) ring <<= 1;
+  d.ring = ring;
+  d.nblocks = ((g.W + 15) / 16) * ((g.H + 15) / 16);
+  for (const DecFrame& df : fr) d.has_p |= df.kind == 2;
+  // the chunk's frames in the host's buffer, for the chains to send their rows to (RGB32 of version 3 / 4 streams)
+  // (RGB24 output in the plane's own layout - pitch = stride, the k_copy_planes case - is streamed too when the chunk is nothing
+  // but coded key frames and stays on the device: BASELINE configs[4])
+  bool all_coded_keys = true;
+  for (int i = 0; i < n; i++) all_coded_keys &= !d.ftypes[f0 + i] && (d.heads[f0 + i] & 15) != 1;
+  d.streamed_rgb24 = d.rows_by_streamer && !d.out_is_host && !v2 && c->bpp == 3 && d.pitch == g.S && ((size_t)d.out & 3) == 0 && all_coded_keys;
+  return SCPR_OK;
+}
+
+// the dense-table cache of a launch (scpr_wave.hpp, WaveModel::tab_of) with what LDS is left behind `dyn` bytes: of the whole CU
+// (160 KiB) when every GOP gets a CU to itself anyway, of half a CU otherwise (two GOPs per CU: a batch of key frames lives on
+// GOPs in flight)
+static int dec_cache_tables(bool has_p, size_t ng, int dyn) {
+  int ndc = 0;
+  const size_t lds_static = has_p ? sizeof(WaveLds) : offsetof(WaveLds, fp);  // (a batch of key frames: without the P-frame tables)
+  const size_t lds_budget = (ng <= 256 ? 160 * 1024 : (has_p || ng <= 512) ? 80 * 1024 : 53 * 1024) - lds_static - 1024;  // one, two or three workgroups per CU
+  while (ndc < 32 && lds_budget > (size_t)dyn && (size_t)dyn + (size_t)(ndc ? 2 * ndc : 1) * sizeof(DenseTab) <= lds_budget) ndc = ndc ? 2 * ndc : 1;
+  if (ndc < 16) ndc = 0;  // a handful of slots would only be evicted all the time (a miss moves two tables, an uncached symbol 32 bytes per lane)
+  return ndc;
+}
+
+// step 2 for one codec: the chunk's own launch on the codec's stream, and the read-back of its error word and arena top
+static int dec_chunk_launch(DecCall& d) {
+  scpr_codec* c = d.c;
+  hipStream_t st = c->stream;
+  const Geom& g = c->g;
+  const size_t ng = d.ng;
+  const bool has_p = d.has_p;
+  if (ng) {
+    const bool v2 = c->version == 2;
+    const int ring = d.ring;
+    Arena ar{c->dec_arena.as<DenseTab>(), c->dec_arena_top.as<u32>(), (u32)d.arena_cap - 1u, c->err.as<u32>()};  // (the last table allocated is the sink)
+    int dyn = ring + (has_p ? ((d.nblocks + 15) & ~15) : 0);  // + one byte per block for P-frames
+    int ndc = 0;
+    const int dcache_off = dyn;
+    if (!v2) {
+      ndc = dec_cache_tables(has_p, ng, dyn);
+      dyn += ndc * (int)sizeof(DenseTab);
+    }
+    const u8* pk = d.pk;
+    const u8* pk_end = pk + d.offs[d.nframes];  // nothing is read at or past this address (the reader supplies 0xFF there)
+    u8* hout = (d.rows_by_streamer && !v2 && (c->bpp == 4 || d.streamed_rgb24)) ? d.out + (size_t)d.f0 * d.pitch * g.H : nullptr;
+    if (v2) {
+      auto kern = has_p ? k_decode_gop_v2<true> : k_decode_gop_v2<false>;
+      HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
+      hipLaunchKernelGGL(kern, dim3((unsigned)ng), dim3(64), dyn, st, pk, pk_end, c->decframes.as<DecFrame>(), c->decgops.as<DecGop>(), c->planes.as<u8>(), g,
+                         c->decstates.as<u32>(), c->err.as<u32>(), ring, c->decfixed.as<V2Fixed>(), (int)c->prm.high_range_x, (int)c->prm.high_range_y);  // the caller's range, unclamped (:76-77)
+    } else {
+      auto kern = has_p ? k_decode_gop_w<true> : k_decode_gop_w<false>;  // key-frame-only GOPs: smaller kernel (instruction cache)
+      HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
+      // P-frame GOPs run as a workgroup: the chain's wave + helper waves for the bulk copies (scpr_wave.hpp, helper_loop) -
+      // eight waves when every GOP has a CU to itself (six helpers: the wave that would share the chain's SIMD leaves at
+      // once), four when CUs are shared (three helpers; two waves per SIMD at most: the chain keeps its 256 registers)
+      static const bool no_helpers = getenv("SCPR_NO_HELPERS") != nullptr;  // (design aid: the chain's wave alone, for the counters of tools/decoder_pmc2.sh)
+      // (a batch of key frames for the host: a second wave per workgroup sends the rows - row_streamer)
+      const unsigned threads = has_p ? (no_helpers ? 64u : ng <= 256 ? 512u : 256u) : hout ? 128u : 64u;
+      hipLaunchKernelGGL(kern, dim3((unsigned)ng), dim3(threads), dyn, st, pk, pk_end, c->decframes.as<DecFrame>(), c->decgops.as<DecGop>(), c->planes.as<u8>(), g,
+                         c->decstates.as<DecRec>(), ar, c->f0, c->err.as<u32>(), ring, c->decfixed.as<FixedBlob>(), (int)std::min<u32>(c->prm.high_range_x, 256),
+                         (int)std::min<u32>(c->prm.high_range_y, 256), ndc, dcache_off, hout, d.pitch, d.n - 1, c->bpp);
+    }
+  }
+  stage_end(c, ST_DECODE);
+  HIPCHK(d2h(c, d.errv, c->err.p, 32, st));
+  if (ng) HIPCHK(d2h(c, &d.atop, c->dec_arena_top.p, 4, st));
+  HIPCHK(sync_out(c, st));  // also covers fr / gops (host memory)
+  HIPCHK(hipGetLastError());         // a kernel that could not be launched
+  return SCPR_OK;
+}
+
+// step 3a: with d.errv / d.atop read back - once more (DEC_AGAIN), or the kept state, the previous plane and the pictures, queued
+// on the codec's stream
+static int dec_chunk_close(DecCall& d) {
+  scpr_codec* c = d.c;
+  hipStream_t st = c->stream;
+  const Geom& g = c->g;
+  const size_t ng = d.ng;
+  const int f0 = d.f0, n = d.n;
+  const u32* errv = d.errv;
+  const u32 atop = d.atop;
+  // A record that names a table beyond the arena's sink (bit 16; refused by the table cache, never followed) is an error of
+  // whatever attempt shows it, and always said: an overflow hands out the sink, so no state the decoder makes by itself holds
+  // such an index.
+  if (errv[0] & 16) fprintf(stderr, "[scpr] decoder: a colour record named a dense table outside the arena (flags %u, attempt %d, %zu GOPs, continued %d)\n", errv[0], d.attempt, ng,
+                            ng ? d.gops[0].load : 0);
+  if ((errv[0] & 1) && d.attempt == 0 && !(ng && d.gops[0].load)) return DEC_AGAIN;  // the estimate was too small for this stream: once more with the true bound
+  if (ng && !(errv[0] & 5)) {
+    // keep the state of the last GOP for the next call; with one GOP in the chunk its tables stay where they are
+    // (top read back: the arena does not grow with the number of calls), with several the next call's first
+    // P-frame would need the last GOP's tables only, which sit anywhere below the top
+    const bool v2 = c->version == 2;
+    const size_t state_bytes = v2 ? (size_t)NCOLCTX * V2_COLTAB * 4 : (size_t)NCOLCTX * sizeof(DecRec);
+    const size_t blob_bytes = v2 ? sizeof(V2Fixed) : sizeof(FixedBlob);
+    HIPCHK(hipMemcpyAsync(c->dec_colour_persist.p, (const u8*)c->decstates.p + (ng - 1) * state_bytes, state_bytes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->dec_fixed_persist.p, (const u8*)c->decfixed.p + (ng - 1) * blob_bytes, blob_bytes, hipMemcpyDeviceToDevice, st));
+    c->dec_arena_used = std::max<size_t>(atop, 1);
+    c->dec_live_bytes = ng > 1 ? d.gop_bytes : c->dec_live_bytes + d.gop_bytes;  // (an upper bound for the GOP that is live after this chunk)
+    c->dec_live = true;
+    if (ng > 1 && !v2 && atop > 1) {  // only the last GOP's tables are needed again: to the bottom (behind table 0), the rest is dropped
+      u32 ntop = 1;
+      int rc = compact_tables(c, c->dec_arena, c->dec_arena2, c->dec_arena_top, c->dec_colour_persist.p, DECREC_WORDS, -1, 0u, 1u, atop, &ntop);
+      if (rc != SCPR_OK) return rc;
+      c->dec_arena_used = std::max<size_t>(ntop, 1);
+    }
+  }
+  HIPCHK(hipMemcpyAsync(c->planes.as<u8>() + (size_t)c->pslot * g.plane_stride, c->planes.as<u8>() + (size_t)(n - 1) * g.plane_stride, g.plane_stride, hipMemcpyDeviceToDevice, st));
+  stage_begin(c, ST_UNPACK);
+  const int pitch = d.pitch;
+  u8* out = d.out + (size_t)f0 * pitch * g.H;
+  if (c->bpp == 4 && d.rows_by_streamer && c->version != 2) {
+    // a chunk of key frames only: the coded ones are at the host already (their workgroups' row streamers sent them); a chunk
+    // with P-frames runs the workgroup form of the kernel, which sends nothing
+    bool chunk_has_p = false;
+    for (int i = 0; i < n; i++) chunk_has_p |= d.ftypes[f0 + i] != 0;
+    std::vector<int> rest;
+    for (int i = 0; i < n; i++) {
+      const bool flat_key = !d.ftypes[f0 + i] && (d.heads[f0 + i] & 15) == 1;
+      if (chunk_has_p || flat_key) rest.push_back(i);
+    }
+    if (!rest.empty()) {
+      HIPCHK(c->hb_list.reserve(rest.size() * 4));
+      HIPCHK(h2d(c, c->hb_list.p, rest.data(), rest.size() * 4, st));
+      dim3 gr((g.H * ((g.W + 3) >> 2) + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS), (unsigned)rest.size());
+      hipLaunchKernelGGL(k_unpack32_list, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g, pitch, c->hb_list.as<int>());
+      HIPCHK(sync_out(c, st));  // (`rest` is host memory)
+    }
+  } else if (c->bpp == 4) {
+    dim3 gr((g.H * ((g.W + 3) >> 2) + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS), n);
+    hipLaunchKernelGGL(k_unpack32, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g, pitch);
+  } else if (c->bpp == 3 && d.streamed_rgb24) {
+    // (the chains' row streamers wrote every picture of the chunk)
+  } else if (c->bpp == 3 && pitch == g.S && ((size_t)out & 3) == 0) {
+    dim3 gr((unsigned)(((size_t)g.H * g.S / 4 + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS)), n);
+    hipLaunchKernelGGL(k_copy_planes, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g);
+  } else {
+    dim3 gr((g.H * g.W + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS), n);
+    hipLaunchKernelGGL(k_unpack_rows, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g, pitch, c->bpp, c->rs, c->gs, c->bs);
+  }
+  stage_end(c, ST_UNPACK);
+  return SCPR_OK;
+}
+
+// step 3b: the chunk's work complete; its outcome.  collect: the codec's timing takes the chunk's stages (decompress_core)
+static int dec_chunk_finish(DecCall& d, bool collect) {
+  scpr_codec* c = d.c;
+  HIPCHK(sync_out(c, c->stream));
+  HIPCHK(hipGetLastError());
+  if (collect) timing_collect(c);
+  const u32 err = d.errv[0];
+  if (err & (1 | 16)) return SCPR_E_DEVICE;  // (an overflow of the arena in a chunk that could not be decoded again also sets 4)
+  if (err & 4) return SCPR_E_STREAM;
+  d.done += d.n;
+  d.f0 += d.n;
+  return SCPR_OK;
+}
+
 // packets resident on the device -> frames at d_frames_out: device memory, or (out_is_host) the host's buffer mapped into the
 // device's address space - then the chains of coded key frames send every finished row there themselves (decode_intra_frame's
 // hdst: the pictures cross PCIe while the chains run) and only what they did not send (P-frames, flat frames; every frame of
 // other pixel formats or of a version 2 stream) is unpacked afterwards, by kernels that write to the host directly.
 static int decompress_core(scpr_codec* c, const void* d_packets, const uint32_t* sizes, const int* ftypes, int nframes, void* d_frames_out, int pitch, bool out_is_host) {
-  hipStream_t st = c->stream;
-  // SCPR_DEV_STREAMER=0: the device-resident output never goes through the row streamer (A/B timing; see rows_by_streamer below)
-  static const bool dev_streamer = !(getenv("SCPR_DEV_STREAMER") && atoi(getenv("SCPR_DEV_STREAMER")) == 0);
+  DecCall d;
+  d.c = c, d.pk = (const u8*)d_packets, d.sizes = sizes, d.ftypes = ftypes, d.nframes = nframes, d.out = (u8*)d_frames_out, d.pitch = pitch, d.out_is_host = out_is_host;
   timing_reset(c);
-  // first bytes of every packet decide version / flat / coded (screencap.cpp:1700, :1536)
-  std::vector<u64> offs(nframes + 1, 0);
-  for (int i = 0; i < nframes; i++) offs[i + 1] = offs[i] + sizes[i];
-  std::vector<u32> heads(nframes, 0);
-  if (nframes) {
-    HIPCHK(c->pktoff.reserve((size_t)(nframes + 1) * 8));
-    HIPCHK(c->outsizes.reserve((size_t)nframes * 4));
-    HIPCHK(h2d(c, c->pktoff.p, offs.data(), (size_t)(nframes + 1) * 8, st));
-    hipLaunchKernelGGL(k_heads, dim3((nframes + 255) / 256), dim3(256), 0, st, (const u8*)d_packets, c->pktoff.as<u64>(), nframes, c->outsizes.as<u32>());
-    HIPCHK(d2h(c, heads.data(), c->outsizes.p, (size_t)nframes * 4, st));
-  }
-  HIPCHK(sync_out(c, st));
-  int done = 0;
+  int rc = dec_heads(d);
+  if (rc != SCPR_OK) return rc;
+  HIPCHK(sync_out(c, c->stream));
   HIPCHK(c->err.reserve(64));
-  for (int f0 = 0; f0 < nframes;) {
-    if (!c->have_codec) {
-      if (ftypes[f0] > 0) return done;  // P-frame before any key frame (:1699)
-      int version = (int)((heads[f0] & 0xFF) >> 4) + 1;
-      int rc = ensure_codec(c, version);
+  while (d.f0 < nframes) {
+    if ((rc = dec_chunk_open(d)) != SCPR_OK) return rc == DEC_STOP ? d.done : rc;
+    for (;; d.attempt++) {
+      if ((rc = dec_chunk_prepare(d, true)) != SCPR_OK) return rc == DEC_STOP ? d.done : rc;
+      if ((rc = dec_chunk_launch(d)) != SCPR_OK) return rc;
+      if ((rc = dec_chunk_close(d)) == DEC_AGAIN) continue;
       if (rc != SCPR_OK) return rc;
+      break;
     }
-    const Geom& g = c->g;
-    // a chunk: as many frames as there are planes for, and no more GOPs than the GPU runs side by side (768 chains)
-    int n = 0;
-    for (int keys = 0; f0 + n < nframes && n < c->dslots; n++)
-      if (ftypes[f0 + n] == 0 && ++keys > 768) break;
-    {
-      int rc = ensure_planes(c, (size_t)n);
-      if (rc != SCPR_OK) return rc;
-    }
-    // A chunk of fresh GOPs is decoded with a dense-table arena sized from its packets (a table per 12 bytes of stream, below);
-    // should that not be enough the device reports an overflow (nothing is lost: the contexts past the end share the sink
-    // table) and the chunk is decoded again with the true bound (every context of every GOP dense, 12288 tables per GOP).
-    const bool host_crashed = c->crashed, host_flat = c->last_flat;
-    const u32 host_flat_rgb = c->last_flat_rgb, host_frames_done = c->frames_done;
-    u32 errv[8] = {0};
-    bool rows_by_streamer = out_is_host;  // (decided per chunk, below)
-    bool streamed_rgb24 = false;          // ... and whether a chunk of RGB24 output went out that way (nothing left to copy then)
-    for (int attempt = 0;; attempt++) {
-    c->crashed = host_crashed, c->last_flat = host_flat, c->last_flat_rgb = host_flat_rgb, c->frames_done = host_frames_done;
-    std::vector<DecFrame> fr;
-    std::vector<DecGop> gops;
-    HIPCHK(hipMemsetAsync(c->err.p, 0, 32, st));
-    stage_begin(c, ST_DECODE);
-    u64 gop_bytes = 0;
-    for (int i = 0; i < n; i++) {
-      const int fi = f0 + i;
-      if (c->crashed && ftypes[fi] > 0) return done;  // (:1697)
-      c->crashed = false;
-      c->frames_done++;
-      DecFrame d{offs[fi], sizes[fi], i, 0, i > 0 ? i - 1 : c->pslot};
-      bool new_gop = false;
-      if (ftypes[fi]) {  // DecompressP
-        d.kind = 2;
-        c->last_flat = false;
-        if (gops.empty()) gops.push_back({(int)fr.size(), 0, c->dec_live ? 1 : 0, 0});
-      } else if ((heads[fi] & 15) == 1) {  // flat key frame (:1537-1553)
-        const u32 rgb = (heads[fi] >> 8) & 0xFFFFFFu;
-        d.kind = 1;
-        hipLaunchKernelGGL(k_fill_flat, dim3((g.H * g.S + 255) / 256), dim3(256), 0, st, c->planes.as<u8>(), g, i, rgb);
-        new_gop = !(c->last_flat && c->last_flat_rgb == rgb);  // models renewed unless the colour repeats
-        c->last_flat = true;
-        c->last_flat_rgb = rgb;
-        if (!new_gop && gops.empty()) gops.push_back({(int)fr.size(), 0, c->dec_live ? 1 : 0, 0});
-      } else {
-        d.kind = 0;
-        c->last_flat = false;
-        new_gop = true;
-      }
-      if (new_gop) gops.push_back({(int)fr.size(), 0, 0, 0});
-      fr.push_back(d);
-      gops.back().count++;
-      gop_bytes += sizes[fi];
-    }
-    const size_t ng = gops.size();
-    // Key frames of RGB32 output leave through their workgroup's row streamer (a second wave that converts the rows the chain has
-    // finished, scpr_wave.hpp) while the chain runs: always when the pictures go to the host (round 4), and since round 5 also
-    // when they stay on the device, as long as the chunk's workgroups are at most two to a CU - chain and streamer then have a
-    // SIMD each, the decode launch takes what it took (114.9 ms) and k_unpack32's 0.8 ms behind it are gone (headline 133.1 ->
-    // 132.1 ms).  With three workgroups on a CU (more than 512 chains in the chunk) streamers share SIMDs with chains and cost
-    // more than the kernel they spare (2400 key frames: 449.8 ms against 422.9 + 6.1): those chunks are unpacked afterwards.
-    static const size_t dev_streamer_max = getenv("SCPR_DEV_STREAMER_MAX") ? (size_t)atoi(getenv("SCPR_DEV_STREAMER_MAX")) : 512;  // (A/B timing)
-    rows_by_streamer = out_is_host || (dev_streamer && ng <= dev_streamer_max);
-    streamed_rgb24 = false;
-    if (ng) {
-      HIPCHK(c->decframes.reserve(fr.size() * sizeof(DecFrame)));
-      HIPCHK(c->decgops.reserve(ng * sizeof(DecGop)));
-      const bool v2 = c->version == 2;  // range-coder streams: count tables instead of context records (scpr_v2.hpp)
-      const size_t state_bytes = v2 ? (size_t)NCOLCTX * V2_COLTAB * 4 : (size_t)NCOLCTX * sizeof(DecRec);
-      const size_t blob_bytes = v2 ? sizeof(V2Fixed) : sizeof(FixedBlob);
-      HIPCHK(c->decstates.reserve(ng * state_bytes));
-      HIPCHK(c->decfixed.reserve(ng * blob_bytes));
-      HIPCHK(c->dec_fixed_persist.reserve(blob_bytes));
-      HIPCHK(c->dec_colour_persist.reserve(state_bytes));
-      if (!v2) HIPCHK(hipMemsetAsync(c->decstates.p, 0, ng * state_bytes, st));  // kind 0 everywhere (RenewI)
-      const bool cont = gops[0].load != 0;
-      if (cont && !v2 && getenv("SCPR_DEBUG_KEYS")) {  // design aid: every table index of the kept records lies inside the kept part of the arena
-        std::vector<u32> hr((size_t)NCOLCTX * DECREC_WORDS);
-        HIPCHK(d2h(c, hr.data(), c->dec_colour_persist.p, hr.size() * 4, st));
-        HIPCHK(sync_out(c, st));
-        size_t bad = 0, dense = 0, firstbad = 0;
-        for (size_t r = 0; r < (size_t)NCOLCTX; r++) {
-          const u32 kind = hr[r * DECREC_WORDS] & 255u;
-          if (kind == 6 || kind == 7) {
-            dense++;
-            if (hr[r * DECREC_WORDS + 2] == 0 || hr[r * DECREC_WORDS + 2] >= c->dec_arena_used) {
-              if (!bad) firstbad = r;
-              bad++;
-            }
-          }
-        }
-        fprintf(stderr, "[scpr debug] continuing GOP: %zu dense records, arena used %zu, bad indices %zu (first record %zu: kind %u index %u)\n", dense, c->dec_arena_used, bad, firstbad,
-                bad ? hr[firstbad * DECREC_WORDS] & 255u : 0u, bad ? hr[firstbad * DECREC_WORDS + 2] : 0u);
-        if (bad) return SCPR_E_DEVICE;
-      }
-      if (cont) {  // the first GOP continues the state kept from the previous call
-        HIPCHK(hipMemcpyAsync(c->decstates.p, c->dec_colour_persist.p, state_bytes, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(c->decfixed.p, c->dec_fixed_persist.p, blob_bytes, hipMemcpyDeviceToDevice, st));
-      } else {
-        c->dec_arena_used = 1;
-        c->dec_live_bytes = 0;
-      }
-      // Tables alive at the end of this chunk.  The true bound is 12288 per GOP.  In practice a context goes dense once, after at
-      // least 16 of its symbols, each of which cost the stream about a byte or more (raw bytes while nothing repeats, one-slot
-      // intervals of a small table after that: ans_contexts.cpp:3-50; a table per 12 bytes of stream has never been seen
-      // exceeded) - counted over the whole GOP, earlier calls included.  The first attempt of a chunk of fresh GOPs gets that
-      // estimate (round 2 gave it a flat 1024 tables per GOP: a GOP of 300 desktop frames overflowed at frame ~220 and was decoded
-      // twice, 8.2 s instead of 4.2), the second attempt - and a chunk that continues a GOP, which cannot be decoded twice: its
-      // run changes the tables that GOP already owns - the true bound.
-      const size_t true_bound = ng * (size_t)NCOLCTX;
-      size_t estimate = std::min<size_t>(true_bound, (size_t)((c->dec_live_bytes + gop_bytes) / 12) + 8 * ng);
-      if (const char* dbg = getenv("SCPR_DEBUG_DEC_ARENA")) estimate = std::min<size_t>(estimate, (size_t)strtoull(dbg, nullptr, 0));  // (tests reach the second attempt)
-      const size_t budget = v2 ? 0 : (attempt || cont) ? true_bound : estimate;
-      // (the arena holds table 0 and the live GOP's tables when a chunk starts: compact_tables after every chunk with several GOPs;
-      // + 1: the sink of an overflow, + slack)
-      const size_t arena_cap = std::min<size_t>(1 + true_bound, c->dec_arena_used + budget) + 1 + 64;
-      HIPCHK(c->dec_arena.reserve_keep(arena_cap * sizeof(DenseTab), c->dec_arena_used * sizeof(DenseTab), st));
-      c->h_dec_top0 = (u32)c->dec_arena_used;  // (a member: the source of an asynchronous copy must outlive the call)
-      HIPCHK(h2d(c, c->dec_arena_top.p, &c->h_dec_top0, 4, st));
-      HIPCHK(h2d(c, c->decframes.p, fr.data(), fr.size() * sizeof(DecFrame), st));
-      HIPCHK(h2d(c, c->decgops.p, gops.data(), ng * sizeof(DecGop), st));
-      Arena ar{c->dec_arena.as<DenseTab>(), c->dec_arena_top.as<u32>(), (u32)arena_cap - 1u, c->err.as<u32>()};  // (the last table allocated is the sink)
-      // LDS ring of 32-bit pixels: the predictors look back one row + 1 pixel, a finished row is flushed at most
-      // one run after it ends, and a run writes up to 255 pixels ahead: a power of two >= W + 512 pixels.
-      // (Keeping static + dynamic LDS under 80 KiB lets two GOPs share a CU.)
-      int ring = 4096;
-      while (ring < 4 * (g.W + 512)) ring <<= 1;
-      const int nblocks = ((g.W + 15) / 16) * ((g.H + 15) / 16);
-      bool has_p = false;
-      for (const DecFrame& d : fr) has_p |= d.kind == 2;
-      int dyn = ring + (has_p ? ((nblocks + 15) & ~15) : 0);  // + one byte per block for P-frames
-      // + the dense-table cache (scpr_wave.hpp, WaveModel::tab_of) with what LDS is left: of the whole CU (160 KiB) when every
-      // GOP gets a CU to itself anyway, of half a CU otherwise (two GOPs per CU: a batch of key frames lives on GOPs in flight)
-      int ndc = 0;
-      const int dcache_off = dyn;
-      if (!v2) {
-        const size_t lds_static = has_p ? sizeof(WaveLds) : offsetof(WaveLds, fp);  // (a batch of key frames: without the P-frame tables)
-        const size_t lds_budget = (ng <= 256 ? 160 * 1024 : (has_p || ng <= 512) ? 80 * 1024 : 53 * 1024) - lds_static - 1024;  // one, two or three workgroups per CU
-        while (ndc < 32 && lds_budget > (size_t)dyn && (size_t)dyn + (size_t)(ndc ? 2 * ndc : 1) * sizeof(DenseTab) <= lds_budget) ndc = ndc ? 2 * ndc : 1;
-        if (ndc < 16) ndc = 0;  // a handful of slots would only be evicted all the time (a miss moves two tables, an uncached symbol 32 bytes per lane)
-        dyn += ndc * (int)sizeof(DenseTab);
-      }
-      const u8* pk = (const u8*)d_packets;
-      const u8* pk_end = pk + offs[nframes];  // nothing is read at or past this address (the reader supplies 0xFF there)
-      // the chunk's frames in the host's buffer, for the chains to send their rows to (RGB32 of version 3 / 4 streams)
-      // (RGB24 output in the plane's own layout - pitch = stride, the k_copy_planes case - is streamed too when the chunk is nothing
-      // but coded key frames and stays on the device: BASELINE configs[4])
-      bool all_coded_keys = true;
-      for (int i = 0; i < n; i++) all_coded_keys &= !ftypes[f0 + i] && (heads[f0 + i] & 15) != 1;
-      streamed_rgb24 = rows_by_streamer && !out_is_host && !v2 && c->bpp == 3 && pitch == g.S && ((size_t)d_frames_out & 3) == 0 && all_coded_keys;
-      u8* hout = (rows_by_streamer && !v2 && (c->bpp == 4 || streamed_rgb24)) ? (u8*)d_frames_out + (size_t)f0 * pitch * g.H : nullptr;
-      if (v2) {
-        auto kern = has_p ? k_decode_gop_v2<true> : k_decode_gop_v2<false>;
-        HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
-        hipLaunchKernelGGL(kern, dim3((unsigned)ng), dim3(64), dyn, st, pk, pk_end, c->decframes.as<DecFrame>(), c->decgops.as<DecGop>(), c->planes.as<u8>(), g,
-                           c->decstates.as<u32>(), c->err.as<u32>(), ring, c->decfixed.as<V2Fixed>(), (int)c->prm.high_range_x, (int)c->prm.high_range_y);  // the caller's range, unclamped (:76-77)
-      } else {
-        auto kern = has_p ? k_decode_gop_w<true> : k_decode_gop_w<false>;  // key-frame-only GOPs: smaller kernel (instruction cache)
-        HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
-        // P-frame GOPs run as a workgroup: the chain's wave + helper waves for the bulk copies (scpr_wave.hpp, helper_loop) -
-        // eight waves when every GOP has a CU to itself (six helpers: the wave that would share the chain's SIMD leaves at
-        // once), four when CUs are shared (three helpers; two waves per SIMD at most: the chain keeps its 256 registers)
-        static const bool no_helpers = getenv("SCPR_NO_HELPERS") != nullptr;  // (design aid: the chain's wave alone, for the counters of tools/decoder_pmc2.sh)
-        // (a batch of key frames for the host: a second wave per workgroup sends the rows - row_streamer)
-        const unsigned threads = has_p ? (no_helpers ? 64u : ng <= 256 ? 512u : 256u) : hout ? 128u : 64u;
-        hipLaunchKernelGGL(kern, dim3((unsigned)ng), dim3(threads), dyn, st, pk, pk_end, c->decframes.as<DecFrame>(), c->decgops.as<DecGop>(), c->planes.as<u8>(), g,
-                           c->decstates.as<DecRec>(), ar, c->f0, c->err.as<u32>(), ring, c->decfixed.as<FixedBlob>(), (int)std::min<u32>(c->prm.high_range_x, 256),
-                           (int)std::min<u32>(c->prm.high_range_y, 256), ndc, dcache_off, hout, pitch, n - 1, c->bpp);
-      }
-    }
-    stage_end(c, ST_DECODE);
-    u32 atop = 0;
-    HIPCHK(d2h(c, errv, c->err.p, 32, st));
-    if (ng) HIPCHK(d2h(c, &atop, c->dec_arena_top.p, 4, st));
-    HIPCHK(sync_out(c, st));  // also covers fr / gops (host memory)
-    HIPCHK(hipGetLastError());         // a kernel that could not be launched
-    // A record that names a table beyond the arena's sink (bit 16; refused by the table cache, never followed) is an error of
-    // whatever attempt shows it, and always said: an overflow hands out the sink, so no state the decoder makes by itself holds
-    // such an index.
-    if (errv[0] & 16) fprintf(stderr, "[scpr] decoder: a colour record named a dense table outside the arena (flags %u, attempt %d, %zu GOPs, continued %d)\n", errv[0], attempt, ng,
-                              ng ? gops[0].load : 0);
-    if ((errv[0] & 1) && attempt == 0 && !(ng && gops[0].load)) continue;  // the estimate was too small for this stream: once more with the true bound
-    if (ng && !(errv[0] & 5)) {
-      // keep the state of the last GOP for the next call; with one GOP in the chunk its tables stay where they are
-      // (top read back: the arena does not grow with the number of calls), with several the next call's first
-      // P-frame would need the last GOP's tables only, which sit anywhere below the top
-      const bool v2 = c->version == 2;
-      const size_t state_bytes = v2 ? (size_t)NCOLCTX * V2_COLTAB * 4 : (size_t)NCOLCTX * sizeof(DecRec);
-      const size_t blob_bytes = v2 ? sizeof(V2Fixed) : sizeof(FixedBlob);
-      HIPCHK(hipMemcpyAsync(c->dec_colour_persist.p, (const u8*)c->decstates.p + (ng - 1) * state_bytes, state_bytes, hipMemcpyDeviceToDevice, st));
-      HIPCHK(hipMemcpyAsync(c->dec_fixed_persist.p, (const u8*)c->decfixed.p + (ng - 1) * blob_bytes, blob_bytes, hipMemcpyDeviceToDevice, st));
-      c->dec_arena_used = std::max<size_t>(atop, 1);
-      c->dec_live_bytes = ng > 1 ? gop_bytes : c->dec_live_bytes + gop_bytes;  // (an upper bound for the GOP that is live after this chunk)
-      c->dec_live = true;
-      if (ng > 1 && !v2 && atop > 1) {  // only the last GOP's tables are needed again: to the bottom (behind table 0), the rest is dropped
-        u32 ntop = 1;
-        int rc = compact_tables(c, c->dec_arena, c->dec_arena2, c->dec_arena_top, c->dec_colour_persist.p, DECREC_WORDS, -1, 0u, 1u, atop, &ntop);
-        if (rc != SCPR_OK) return rc;
-        c->dec_arena_used = std::max<size_t>(ntop, 1);
-      }
-    }
-    break;
-    }
-    HIPCHK(hipMemcpyAsync(c->planes.as<u8>() + (size_t)c->pslot * g.plane_stride, c->planes.as<u8>() + (size_t)(n - 1) * g.plane_stride, g.plane_stride, hipMemcpyDeviceToDevice, st));
-    stage_begin(c, ST_UNPACK);
-    u8* out = (u8*)d_frames_out + (size_t)f0 * pitch * g.H;
-    if (c->bpp == 4 && rows_by_streamer && c->version != 2) {
-      // a chunk of key frames only: the coded ones are at the host already (their workgroups' row streamers sent them); a chunk
-      // with P-frames runs the workgroup form of the kernel, which sends nothing
-      bool chunk_has_p = false;
-      for (int i = 0; i < n; i++) chunk_has_p |= ftypes[f0 + i] != 0;
-      std::vector<int> rest;
-      for (int i = 0; i < n; i++) {
-        const bool flat_key = !ftypes[f0 + i] && (heads[f0 + i] & 15) == 1;
-        if (chunk_has_p || flat_key) rest.push_back(i);
-      }
-      if (!rest.empty()) {
-        HIPCHK(c->hb_list.reserve(rest.size() * 4));
-        HIPCHK(h2d(c, c->hb_list.p, rest.data(), rest.size() * 4, st));
-        dim3 gr((g.H * ((g.W + 3) >> 2) + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS), (unsigned)rest.size());
-        hipLaunchKernelGGL(k_unpack32_list, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g, pitch, c->hb_list.as<int>());
-        HIPCHK(sync_out(c, st));  // (`rest` is host memory)
-      }
-    } else if (c->bpp == 4) {
-      dim3 gr((g.H * ((g.W + 3) >> 2) + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS), n);
-      hipLaunchKernelGGL(k_unpack32, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g, pitch);
-    } else if (c->bpp == 3 && streamed_rgb24) {
-      // (the chains' row streamers wrote every picture of the chunk)
-    } else if (c->bpp == 3 && pitch == g.S && ((size_t)out & 3) == 0) {
-      dim3 gr((unsigned)(((size_t)g.H * g.S / 4 + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS)), n);
-      hipLaunchKernelGGL(k_copy_planes, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g);
-    } else {
-      dim3 gr((g.H * g.W + 256 * PACK_ITEMS - 1) / (256 * PACK_ITEMS), n);
-      hipLaunchKernelGGL(k_unpack_rows, gr, dim3(256), 0, st, c->planes.as<u8>(), out, g, pitch, c->bpp, c->rs, c->gs, c->bs);
-    }
-    stage_end(c, ST_UNPACK);
-    HIPCHK(sync_out(c, st));
-    HIPCHK(hipGetLastError());
-    timing_collect(c);
-    const u32 err = errv[0];
-    if (err & (1 | 16)) return SCPR_E_DEVICE;  // (an overflow of the arena in a chunk that could not be decoded again also sets 4)
-    if (err & 4) return SCPR_E_STREAM;
-    done += n;
-    f0 += n;
+    if ((rc = dec_chunk_finish(d, true)) != SCPR_OK) return rc;
   }
-  return done;
+  return d.done;
 }
 
 int scpr_decompress_batch(scpr_codec* c, const void* d_packets, const uint32_t* sizes, const int* ftypes, int nframes, void* d_frames_out, int pitch) {
@@ -1768,6 +1876,202 @@ int scpr_decompress_batch(scpr_codec* c, const void* d_packets, const uint32_t* 
   if (hipSetDevice(c->device) != hipSuccess) return SCPR_E_DEVICE;
   pin_reset(c);
   return decompress_core(c, d_packets, sizes, ftypes, nframes, d_frames_out, pitch, false);
+}
+
+// ---- many codecs' GOPs in one launch ------------------------------------------------------------------------------------------
+// Rounds: every codec with frames left prepares its next chunk (the same chunk decompress_core would decode: dslots planes,
+// <= 768 GOPs) on its own stream; chunks go into one launch of k_decode_streams_w until it holds 768 GOPs (a chunk that does not
+// fit waits, prepared, for the next round); the launch goes on the stream of the call's first codec behind every participant's
+// own stream; one read-back brings every status word and arena top; then every codec's epilogue runs on its own stream.  A
+// codec whose fresh chunk overflowed its arena estimate prepares it again with the true bound and joins the next round.
+int scpr_decompress_streams(scpr_decode_call* calls, int ncalls) {
+  if (!calls || ncalls < 0) return SCPR_E_PARAM;
+  if (ncalls == 0) return SCPR_OK;
+  std::vector<scpr_codec*> seen;
+  seen.reserve((size_t)ncalls);
+  for (int i = 0; i < ncalls; i++) {
+    const scpr_decode_call& e = calls[i];
+    if (!e.codec || !e.codec->inited || !e.d_packets || !e.sizes || !e.ftypes || !e.d_frames_out || e.nframes < 0) return SCPR_E_PARAM;
+    if (e.codec->device != calls[0].codec->device) return SCPR_E_PARAM;
+    seen.push_back(e.codec);
+  }
+  std::sort(seen.begin(), seen.end());
+  if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return SCPR_E_PARAM;  // the same codec twice
+  scpr_codec* lead = calls[0].codec;
+  if (hipSetDevice(lead->device) != hipSuccess) {
+    for (int i = 0; i < ncalls; i++) calls[i].result = SCPR_E_DEVICE;
+    return SCPR_OK;
+  }
+  const hipStream_t ls = lead->stream;
+  enum { OPEN, PREPARE, READY, CLOSE, DONE };
+  std::vector<DecCall> d((size_t)ncalls);
+  std::vector<int> state((size_t)ncalls, OPEN);
+  std::vector<char> joint((size_t)ncalls, 1);  // timed as a participant of the joint launches (version 2 streams are not)
+  auto end = [&](int i, int r) {
+    calls[i].result = r;
+    state[i] = DONE;
+  };
+  for (int i = 0; i < ncalls; i++) {
+    scpr_codec* c = calls[i].codec;
+    pin_reset(c);
+    timing_reset(c);
+    calls[i].result = 0;
+    DecCall& x = d[i];
+    x.c = c, x.pk = (const u8*)calls[i].d_packets, x.sizes = calls[i].sizes, x.ftypes = calls[i].ftypes, x.nframes = calls[i].nframes;
+    x.out = (u8*)calls[i].d_frames_out, x.pitch = calls[i].pitch;
+    const int rc = dec_heads(x);
+    if (rc != SCPR_OK) end(i, rc);
+  }
+  for (int i = 0; i < ncalls; i++) {
+    if (state[i] == DONE) continue;
+    scpr_codec* c = d[i].c;
+    if (sync_out(c, c->stream) != hipSuccess || c->err.reserve(64) != hipSuccess) {
+      end(i, SCPR_E_DEVICE);
+      continue;
+    }
+    // version 2 (range-coder) streams: decoded by the codec's own path
+    const bool v2 = c->have_codec ? c->version == 2 : (d[i].nframes > 0 && d[i].ftypes[0] == 0 && ((d[i].heads[0] & 0xFF) >> 4) + 1 == 2);
+    if (v2) {
+      joint[i] = 0;
+      end(i, decompress_core(c, calls[i].d_packets, calls[i].sizes, calls[i].ftypes, calls[i].nframes, calls[i].d_frames_out, calls[i].pitch, false));
+    }
+  }
+  float decode_ms = 0, unpack_ms = 0;
+  bool launch_failed = false;
+  std::vector<StreamDesc> sd;
+  std::vector<GopRef> refs;
+  std::vector<int> in;
+  std::vector<u32> status;
+  for (;;) {
+    // chunks into this round's launch
+    in.clear();
+    size_t total = 0;
+    for (int i = 0; i < ncalls; i++) {
+      DecCall& x = d[i];
+      if (state[i] == OPEN) {
+        if (x.f0 >= x.nframes) {
+          end(i, x.done);
+          continue;
+        }
+        const int rc = dec_chunk_open(x);
+        if (rc != SCPR_OK) {
+          end(i, rc == DEC_STOP ? x.done : rc);
+          continue;
+        }
+        state[i] = PREPARE;
+      }
+      if (state[i] == PREPARE) {
+        const int rc = dec_chunk_prepare(x, false);
+        if (rc != SCPR_OK) {
+          end(i, rc == DEC_STOP ? x.done : rc);
+          continue;
+        }
+        state[i] = READY;
+      }
+      if (state[i] == READY && (total == 0 || total + x.ng <= 768)) {
+        in.push_back(i);
+        total += x.ng;
+      }
+    }
+    if (in.empty()) break;
+    // the launch: descriptors, GOP list, LDS layout for the widest stream
+    sd.clear();
+    refs.clear();
+    int ring = 0, nblocks = 0;
+    bool has_p = false;
+    for (int i : in) {
+      DecCall& x = d[i];
+      scpr_codec* c = x.c;
+      if (c != lead) {  // (its preparation, queued on its own stream, comes first)
+        (void)hipEventRecord(c->ev_fork, c->stream);
+        (void)hipStreamWaitEvent(ls, c->ev_fork, 0);
+      }
+      if (!x.ng) continue;
+      Arena ar{c->dec_arena.as<DenseTab>(), c->dec_arena_top.as<u32>(), (u32)x.arena_cap - 1u, c->err.as<u32>()};  // (the last table allocated is the sink)
+      for (size_t k = 0; k < x.ng; k++) refs.push_back({(int)sd.size(), (int)k, (int)k, 0});
+      sd.push_back({x.pk, x.pk + x.offs[x.nframes], c->decframes.as<DecFrame>(), c->decgops.as<DecGop>(), c->planes.as<u8>(), c->decstates.as<DecRec>(),
+                    c->decfixed.as<FixedBlob>(), c->err.as<u32>(), ar, c->g, c->f0, x.ring, (int)std::min<u32>(c->prm.high_range_x, 256),
+                    (int)std::min<u32>(c->prm.high_range_y, 256)});
+      ring = std::max(ring, x.ring);
+      nblocks = std::max(nblocks, x.nblocks);
+      has_p |= x.has_p;
+    }
+    int rc = SCPR_OK;
+    const size_t ng = refs.size();
+    if (ng) {
+      int dyn = ring + (has_p ? ((nblocks + 15) & ~15) : 0);  // + one byte per block for P-frames
+      const int dcache_off = dyn;
+      const int ndc = dec_cache_tables(has_p, ng, dyn);
+      dyn += ndc * (int)sizeof(DenseTab);
+      static const bool no_helpers = getenv("SCPR_NO_HELPERS") != nullptr;
+      const unsigned threads = has_p ? (no_helpers ? 64u : ng <= 256 ? 512u : 256u) : 64u;
+      auto kern = has_p ? k_decode_streams_w<true> : k_decode_streams_w<false>;
+      const int ns = (int)sd.size();
+      if (lead->ms_streams.reserve(sd.size() * sizeof(StreamDesc)) != hipSuccess || lead->ms_refs.reserve(ng * sizeof(GopRef)) != hipSuccess ||
+          lead->ms_status.reserve(sd.size() * 8) != hipSuccess || h2d(lead, lead->ms_streams.p, sd.data(), sd.size() * sizeof(StreamDesc), ls) != hipSuccess ||
+          h2d(lead, lead->ms_refs.p, refs.data(), ng * sizeof(GopRef), ls) != hipSuccess ||
+          hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess) {
+        rc = SCPR_E_DEVICE;
+      } else {
+        (void)hipEventRecord(lead->ev[ST_DECODE][0], ls);
+        hipLaunchKernelGGL(kern, dim3((unsigned)ng), dim3(threads), dyn, ls, lead->ms_streams.as<StreamDesc>(), lead->ms_refs.as<GopRef>(), ndc, dcache_off);
+        (void)hipEventRecord(lead->ev[ST_DECODE][1], ls);
+        if (hipGetLastError() != hipSuccess) rc = SCPR_E_DEVICE;  // (a kernel that could not be launched)
+        hipLaunchKernelGGL(k_stream_status, dim3((ns + 255) / 256), dim3(256), 0, ls, lead->ms_streams.as<StreamDesc>(), ns, lead->ms_status.as<u32>());
+        status.assign((size_t)ns * 2, 0);
+        if (d2h(lead, status.data(), lead->ms_status.p, (size_t)ns * 8, ls) != hipSuccess) rc = SCPR_E_DEVICE;
+      }
+      if (sync_out(lead, ls) != hipSuccess || hipGetLastError() != hipSuccess) rc = SCPR_E_DEVICE;
+      float ms = 0;
+      if (rc == SCPR_OK && hipEventElapsedTime(&ms, lead->ev[ST_DECODE][0], lead->ev[ST_DECODE][1]) == hipSuccess) decode_ms += ms;
+    } else if (sync_out(lead, ls) != hipSuccess) {
+      rc = SCPR_E_DEVICE;
+    }
+    if (rc != SCPR_OK) {
+      launch_failed = true;
+      for (int i : in) end(i, SCPR_E_DEVICE);
+      continue;
+    }
+    // epilogues: queued codec by codec, then waited for
+    int s = 0;
+    for (int i : in) {
+      DecCall& x = d[i];
+      if (x.ng) {
+        x.errv[0] = status[2 * s], x.atop = status[2 * s + 1];
+        s++;
+      }
+      const int r = dec_chunk_close(x);
+      if (r == DEC_AGAIN) {
+        x.attempt++;
+        state[i] = PREPARE;
+      } else if (r != SCPR_OK) {
+        end(i, r);
+      } else {
+        state[i] = CLOSE;
+      }
+    }
+    for (int i : in) {
+      if (state[i] != CLOSE) continue;
+      DecCall& x = d[i];
+      scpr_codec* c = x.c;
+      const int r = dec_chunk_finish(x, false);
+      float ms = 0;
+      if (c->ev_used[ST_UNPACK] && hipEventElapsedTime(&ms, c->ev[ST_UNPACK][0], c->ev[ST_UNPACK][1]) == hipSuccess) unpack_ms += ms;
+      c->ev_used[ST_UNPACK] = false;
+      if (r != SCPR_OK) end(i, r);
+      else state[i] = OPEN;
+    }
+  }
+  // the call's decode and unpack stages, on every codec that took part in its launches
+  for (int i = 0; i < ncalls; i++) {
+    if (!joint[i]) continue;
+    scpr_codec* c = calls[i].codec;
+    timing_reset(c);
+    c->stage_ms[ST_DECODE] = decode_ms;
+    c->stage_ms[ST_UNPACK] = unpack_ms;
+    c->total_ms = decode_ms + unpack_ms;
+  }
+  return launch_failed ? SCPR_E_DEVICE : SCPR_OK;
 }
 
 // ---- batch entry points with HOST pointers ------------------------------------------------------------------------------------

@@ -2623,15 +2623,14 @@ __device__ __forceinline__ void row_streamer(const u32* rows_word, u32* taken_wo
   }
 }
 
+// The decoder of one GOP, for a workgroup of either launch form below: GOP `gi` of `gops`, its colour records and fixed models in
+// slot `slot` of `states` / `fixedstore`.  L: the workgroup's static LDS; pix: its dynamic LDS.
 template <bool HAS_P>
-__global__ __launch_bounds__(HAS_P ? 512 : 128) void k_decode_gop_w(const u8* __restrict__ packets, const u8* packets_end, const DecFrame* __restrict__ frames, const DecGop* __restrict__ gops,
-                                                     u8* __restrict__ planes, Geom g, DecRec* __restrict__ states, Arena arena, int f0, u32* __restrict__ status, int ring_bytes,
-                                                     FixedBlob* __restrict__ fixedstore, int far_x, int far_y, int ndc, int dcache_off, u8* __restrict__ hout, int hpitch, int keep_slot, int hbpp) {
-  __shared__ __attribute__((aligned(16))) u8 Lraw[HAS_P ? sizeof(WaveLds) : offsetof(WaveLds, fp)];
-  WaveLds& L = *(WaveLds*)Lraw;
-  // ring_bytes = 4 * (power of two >= W + 512) pixels, then (P-frames) one byte per 16x16 block, then (at dcache_off) ndc dense tables
-  extern __shared__ __align__(16) u8 pix[];
-  const DecGop gop = gops[blockIdx.x];
+__device__ __forceinline__ void decode_gop_body(WaveLds& L, u8* pix, u32 gi, u32 slot, const u8* packets, const u8* packets_end, const DecFrame* frames,
+                                                const DecGop* gops, u8* planes, Geom g, DecRec* states, Arena arena, int f0,
+                                                u32* status, int ring_bytes, FixedBlob* fixedstore, int far_x, int far_y, int ndc, int dcache_off,
+                                                u8* hout, int hpitch, int keep_slot, int hbpp) {
+  const DecGop gop = gops[gi];
   const int lane = lane_id();
   // A batch of key frames for the host (hout): the workgroup has a second wave, the row streamer of its coded key frame (a GOP
   // of this kernel holds one, its first frame; the frames after it can only be flat ones).
@@ -2662,7 +2661,7 @@ __global__ __launch_bounds__(HAS_P ? 512 : 128) void k_decode_gop_w(const u8* __
       return;
     }
   }
-  WaveDec D(L, packets, packets_end, states + (size_t)blockIdx.x * NCOLCTX, arena, f0);
+  WaveDec D(L, packets, packets_end, states + (size_t)slot * NCOLCTX, arena, f0);
   D.has_p = HAS_P;
   if (ndc) {
     D.dcache = pix + dcache_off;
@@ -2670,7 +2669,7 @@ __global__ __launch_bounds__(HAS_P ? 512 : 128) void k_decode_gop_w(const u8* __
     D.dmask = (u32)ndc - 1u;
     D.dc_lds = (u32)(size_t)D.dcache;
   }
-  if (gop.load) D.fixed_load(&fixedstore[blockIdx.x]);
+  if (gop.load) D.fixed_load(&fixedstore[slot]);
   else D.fixed_init();
   for (int fi = gop.first; fi < gop.first + gop.count && !D.bad && !D.oom; fi++) {
     const DecFrame fr = frames[fi];
@@ -2692,7 +2691,7 @@ __global__ __launch_bounds__(HAS_P ? 512 : 128) void k_decode_gop_w(const u8* __
   if (HAS_P && L.hc.nhelp) help_post(L, HOP_EXIT, nullptr, nullptr, 0);
   D.flush_records();
   D.flush_tabs();
-  D.fixed_store(&fixedstore[blockIdx.x]);
+  D.fixed_store(&fixedstore[slot]);
   if (D.bad && lane == 0) atomicOr(status, 4u);
 #ifdef SCPR_PROFILE
   if (lane == 0)
@@ -2704,6 +2703,63 @@ __global__ __launch_bounds__(HAS_P ? 512 : 128) void k_decode_gop_w(const u8* __
     for (int i = 0; i < 4; i++) atomicAdd((unsigned long long*)&g_cprof[24 + i], (unsigned long long)D.xprof[i]);
   }
 #endif
+}
+
+template <bool HAS_P>
+__global__ __launch_bounds__(HAS_P ? 512 : 128) void k_decode_gop_w(const u8* __restrict__ packets, const u8* packets_end, const DecFrame* __restrict__ frames, const DecGop* __restrict__ gops,
+                                                     u8* __restrict__ planes, Geom g, DecRec* __restrict__ states, Arena arena, int f0, u32* __restrict__ status, int ring_bytes,
+                                                     FixedBlob* __restrict__ fixedstore, int far_x, int far_y, int ndc, int dcache_off, u8* __restrict__ hout, int hpitch, int keep_slot, int hbpp) {
+  __shared__ __attribute__((aligned(16))) u8 Lraw[HAS_P ? sizeof(WaveLds) : offsetof(WaveLds, fp)];
+  // ring_bytes = 4 * (power of two >= W + 512) pixels, then (P-frames) one byte per 16x16 block, then (at dcache_off) ndc dense tables
+  extern __shared__ __align__(16) u8 pix[];
+  decode_gop_body<HAS_P>(*(WaveLds*)Lraw, pix, blockIdx.x, blockIdx.x, packets, packets_end, frames, gops, planes, g, states, arena, f0, status, ring_bytes, fixedstore,
+                         far_x, far_y, ndc, dcache_off, hout, hpitch, keep_slot, hbpp);
+}
+
+// ---------------------------------------------------------------------------------------
+// Many streams in one launch (scpr_decompress_streams): what k_decode_gop_w takes as launch arguments, per stream, and per
+// workgroup the GOP it decodes.  A stream's lists, planes, records, arena and status word are its codec's own.
+struct StreamDesc {
+  const u8* packets;
+  const u8* packets_end;
+  const DecFrame* frames;
+  const DecGop* gops;
+  u8* planes;
+  DecRec* states;
+  FixedBlob* fixedstore;
+  u32* status;
+  Arena arena;
+  Geom g;
+  int f0;          // 32 (version 3) or 64 (version 4)
+  int ring_bytes;  // the stream's own ring (the launch's LDS is laid out for its widest stream)
+  int far_x, far_y;
+};
+struct GopRef {
+  int stream;  // index into the launch's StreamDesc list
+  int gop;     // index into that stream's DecGop list
+  int slot;    // its colour records / fixed models in the stream's states / fixedstore
+  int pad;
+};
+// Workgroup b decodes refs[b].  Dynamic LDS: the widest stream's ring, then one byte per block of the stream with the most blocks,
+// then (at dcache_off, one place for every stream) ndc dense tables.  No row streamer: every plane is written and the pictures
+// leave through the unpack kernels.
+template <bool HAS_P>
+__global__ __launch_bounds__(HAS_P ? 512 : 64) void k_decode_streams_w(const StreamDesc* __restrict__ streams, const GopRef* __restrict__ refs, int ndc, int dcache_off) {
+  __shared__ __attribute__((aligned(16))) u8 Lraw[HAS_P ? sizeof(WaveLds) : offsetof(WaveLds, fp)];
+  extern __shared__ __align__(16) u8 pix[];
+  const GopRef r = refs[blockIdx.x];
+  const StreamDesc s = streams[r.stream];
+  decode_gop_body<HAS_P>(*(WaveLds*)Lraw, pix, (u32)r.gop, (u32)r.slot, s.packets, s.packets_end, s.frames, s.gops, s.planes, s.g, s.states, s.arena, s.f0, s.status, s.ring_bytes,
+                         s.fixedstore, s.far_x, s.far_y, ndc, dcache_off, nullptr, 0, -1, 0);
+}
+
+// after such a launch: every stream's status word and arena top, side by side (one read-back for all of them)
+__global__ __launch_bounds__(256) void k_stream_status(const StreamDesc* __restrict__ streams, int n, u32* __restrict__ out) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < n) {
+    out[2 * i] = *streams[i].status;
+    out[2 * i + 1] = *streams[i].arena.top;
+  }
 }
 
 // ------------------------------------------------------------- encoder chains ---
