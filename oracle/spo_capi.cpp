@@ -46,6 +46,9 @@ int spo_decompress_frame(void* h, const uint8_t* src, int src_len, uint8_t* dst,
 }
 void spo_crash_happened(void* h) { ((ScreenCodec*)h)->crash_happened(); }
 void spo_set_threads(void* h, int n) { ((ScreenCodec*)h)->set_threads(n); }
+// Test support: encode P-frames as a `workers`-thread reference would under the interleaving drawn from `seed`
+// (FrameCodec::decide_blocks); workers = 0 restores the canonical single-worker order.
+void spo_set_p_race(void* h, int workers, uint64_t seed) { ((ScreenCodec*)h)->set_p_race(workers, seed); }
 void spo_seed_shard(void* h, uint32_t frames_before, int last_flat, uint32_t rgb) {
   const uint8_t c[3] = {(uint8_t)rgb, (uint8_t)(rgb >> 8), (uint8_t)(rgb >> 16)};
   ((ScreenCodec*)h)->seed_shard(frames_before, last_flat != 0, c);

@@ -609,106 +609,170 @@ static inline bool edge_fits(int t, const uint8_t* p, const uint8_t* pr, const u
   return false;
 }
 
-// DecideBlockTypes in canonical order (one worker, block rows top to bottom),
-// :928-1087.  With one worker every row above is Done, so the upper block's
-// vector is always a candidate for by > 0.
-void FrameCodec::decide_blocks(const uint8_t* src, int& obx1, int& obx2, int& oby1, int& oby2) {
-  int bx1 = nbx, bx2 = -1, by1 = nby, by2 = -1;
-  int lmx = 0, lmy = 0;
+// One block row of DecideBlockTypes (:979-1077) with the vector chain (lmx, lmy) of the worker that claimed it.
+// use_upper is canUseUpper (:969-972): the row above was Done when this row was claimed.
+void FrameCodec::decide_row(const uint8_t* src, int by, bool use_upper, int& lmx, int& lmy, int& bx1, int& bx2, int& by1, int& by2) {
   const int off = -stride_ - 3;
   const uint8_t* pv = prev_.data();
   uint8_t* rec = last_records.data();
-  for (int by = 0; by < nby; by++) {
-    size_t j = (size_t)by * 16 * W * 5;
-    band_start_[by] = (uint32_t)j;
-    for (int bx = 0; bx < nbx; bx++) {
-      const int x1 = bx * 16, x2 = imin(bx * 16 + 16, W), y1 = by * 16, y2 = imin(by * 16 + 16, H);
-      const int bi = by * nbx + bx, upper = by > 0 ? bi - nbx : -1;
-      const int bw = (x2 - x1) * 3, xb = x1 * 3;
-      int cp = 0;
-      bool changed = false;
-      auto differs = [&](int x, int y) { return !eq3(src + y * stride_ + x * 3, pv + y * stride_ + x * 3); };
-      for (int y = y1; y < y2; y++) {
-        if (!memcmp(src + y * stride_ + xb, pv + y * stride_ + xb, bw)) continue;
-        changed = true;
-        int sx1 = x2, sx2 = x1, sy1 = y, sy2 = y;
-        for (int yy = y2 - 1; yy > sy1; yy--)
-          if (memcmp(src + yy * stride_ + xb, pv + yy * stride_ + xb, bw)) {
-            sy2 = yy;
-            break;
-          }
-        for (int x = x1; x < x2; x++)
-          if (differs(x, sy2)) {
+  size_t j = (size_t)by * 16 * W * 5;
+  band_start_[by] = (uint32_t)j;
+  for (int bx = 0; bx < nbx; bx++) {
+    const int x1 = bx * 16, x2 = imin(bx * 16 + 16, W), y1 = by * 16, y2 = imin(by * 16 + 16, H);
+    const int bi = by * nbx + bx, upper = use_upper ? bi - nbx : -1;
+    const int bw = (x2 - x1) * 3, xb = x1 * 3;
+    int cp = 0;
+    bool changed = false;
+    auto differs = [&](int x, int y) { return !eq3(src + y * stride_ + x * 3, pv + y * stride_ + x * 3); };
+    for (int y = y1; y < y2; y++) {
+      if (!memcmp(src + y * stride_ + xb, pv + y * stride_ + xb, bw)) continue;
+      changed = true;
+      int sx1 = x2, sx2 = x1, sy1 = y, sy2 = y;
+      for (int yy = y2 - 1; yy > sy1; yy--)
+        if (memcmp(src + yy * stride_ + xb, pv + yy * stride_ + xb, bw)) {
+          sy2 = yy;
+          break;
+        }
+      for (int x = x1; x < x2; x++)
+        if (differs(x, sy2)) {
+          sx1 = x;
+          break;
+        }
+      sx2 = sx1;
+      for (int x = x2 - 1; x > sx1; x--)
+        if (differs(x, sy2)) {
+          sx2 = x;
+          break;
+        }
+      for (int yy = sy1; yy < sy2; yy++) {
+        for (int x = x1; x < sx1; x++)
+          if (differs(x, yy)) {
             sx1 = x;
             break;
           }
-        sx2 = sx1;
-        for (int x = x2 - 1; x > sx1; x--)
-          if (differs(x, sy2)) {
+        for (int x = x2 - 1; x > sx2; x--)
+          if (differs(x, yy)) {
             sx2 = x;
             break;
           }
+      }
+      sx2++;
+      sy2++;
+      if (sx1 > x1 || sy1 > y1 || sx2 < x2 || sy2 < y2) {
+        cp = 2;
+        rect_xy[0][bi] = sx1;
+        rect_xy[1][bi] = sy1;
+        rect_xy[2][bi] = sx2;
+        rect_xy[3][bi] = sy2;
+      } else {
+        cp = 1;
+        rect_xy[0][bi] = x1;
+        rect_xy[1][bi] = y1;
+        rect_xy[2][bi] = x2;
+        rect_xy[3][bi] = y2;
+      }
+      if (find_motion(src, bi, lmx, lmy, upper))
+        cp += 2;
+      else {
+        int n = 333, lasti = 0, t = 0;
         for (int yy = sy1; yy < sy2; yy++) {
-          for (int x = x1; x < sx1; x++)
-            if (differs(x, yy)) {
-              sx1 = x;
-              break;
+          int i = yy * stride_ + sx1 * 3;
+          for (int x = sx1; x < sx2; x++) {
+            const bool inner = x > 0 && yy > 0;
+            bool fits = n < 255 && (inner ? inter_fits(t, src + i, pv + i, src + lasti, off) : edge_fits(t, src + i, pv + i, src + lasti));
+            if (fits)
+              n++;
+            else {
+              if (n != 333) rec[j++] = (uint8_t)n;
+              t = inner ? inter_type(src + i, pv + i, off) : edge_type(src + i, pv + i);
+              rec[j++] = (uint8_t)t;
+              n = 1;
             }
-          for (int x = x2 - 1; x > sx2; x--)
-            if (differs(x, yy)) {
-              sx2 = x;
-              break;
-            }
-        }
-        sx2++;
-        sy2++;
-        if (sx1 > x1 || sy1 > y1 || sx2 < x2 || sy2 < y2) {
-          cp = 2;
-          rect_xy[0][bi] = sx1;
-          rect_xy[1][bi] = sy1;
-          rect_xy[2][bi] = sx2;
-          rect_xy[3][bi] = sy2;
-        } else {
-          cp = 1;
-          rect_xy[0][bi] = x1;
-          rect_xy[1][bi] = y1;
-          rect_xy[2][bi] = x2;
-          rect_xy[3][bi] = y2;
-        }
-        if (find_motion(src, bi, lmx, lmy, upper))
-          cp += 2;
-        else {
-          int n = 333, lasti = 0, t = 0;
-          for (int yy = sy1; yy < sy2; yy++) {
-            int i = yy * stride_ + sx1 * 3;
-            for (int x = sx1; x < sx2; x++) {
-              const bool inner = x > 0 && yy > 0;
-              bool fits = n < 255 && (inner ? inter_fits(t, src + i, pv + i, src + lasti, off) : edge_fits(t, src + i, pv + i, src + lasti));
-              if (fits)
-                n++;
-              else {
-                if (n != 333) rec[j++] = (uint8_t)n;
-                t = inner ? inter_type(src + i, pv + i, off) : edge_type(src + i, pv + i);
-                rec[j++] = (uint8_t)t;
-                n = 1;
-              }
-              lasti = i;
-              i += 3;
-            }
+            lasti = i;
+            i += 3;
           }
-          rec[j++] = (uint8_t)n;
         }
-        break;
+        rec[j++] = (uint8_t)n;
       }
-      blk_types[bi] = (uint8_t)cp;
-      if (changed) {
-        bx1 = imin(bx, bx1);
-        by1 = imin(by, by1);
-        bx2 = imax(bx, bx2);
-        by2 = imax(by, by2);
-      }
+      break;
     }
-    band_size_[by] = (uint32_t)(j - band_start_[by]);
+    blk_types[bi] = (uint8_t)cp;
+    if (changed) {
+      bx1 = imin(bx, bx1);
+      by1 = imin(by, by1);
+      bx2 = imax(bx, bx2);
+      by2 = imax(by, by2);
+    }
+  }
+  band_size_[by] = (uint32_t)(j - band_start_[by]);
+}
+
+static inline uint64_t splitmix64(uint64_t& s) {
+  uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// DecideBlockTypes, :928-1087.  Canonical order (race_workers_ == 0): one worker, block rows top to bottom, so every
+// row above is Done and the upper block's vector is always a candidate for by > 0.
+// With race_workers_ = W the W workers of the reference's pool run the same loop under one seeded interleaving of its
+// critical section (:940-975): a live worker drawn from the seed marks its last row Done and claims the next one - its
+// own GetSegment(nby) band first, then rows stolen in (by + nby - i) % nby order.  The claimed row is then decided in
+// full with that worker's own vector chain.  Rows see each other only through mv[upper] once `upper` is Done, so every
+// stream this writes is one the reference writes under some thread timing.  The row records stay in per-row slots and
+// the changed region is a min / max over rows, so the output order does not depend on the interleaving.
+void FrameCodec::decide_blocks(const uint8_t* src, int& obx1, int& obx2, int& oby1, int& oby2) {
+  int bx1 = nbx, bx2 = -1, by1 = nby, by2 = -1;
+  if (race_workers_ <= 0) {
+    int lmx = 0, lmy = 0;
+    for (int by = 0; by < nby; by++) decide_row(src, by, by > 0, lmx, lmy, bx1, bx2, by1, by2);
+  } else {
+    enum { kUntouched = 0, kProcessing = 1, kDone = 2 };
+    struct Worker {
+      int phase, by, by_end, just_finished, lmx, lmy;
+    };
+    const int nw = race_workers_;
+    std::vector<uint8_t> state((size_t)nby, kUntouched);
+    std::vector<Worker> wk((size_t)nw);
+    std::vector<int> live((size_t)nw);
+    for (int k = 0; k < nw; k++) {
+      int start = 0, size = 0;
+      segment(nby, k, nw, start, size);
+      wk[k] = {1, start, start + size, -1, 0, 0};
+      live[k] = k;
+    }
+    while (!live.empty()) {
+      const size_t pick = (size_t)(splitmix64(race_rng_) % live.size());
+      Worker& w = wk[live[pick]];
+      if (w.just_finished >= 0) state[w.just_finished] = kDone;
+      bool found = false;
+      if (w.phase == 1) {
+        while (w.by < w.by_end && state[w.by] != kUntouched) w.by++;
+        if (w.by == w.by_end)
+          w.phase = 2;
+        else
+          found = true;
+      }
+      if (w.phase == 2) {
+        for (int i = 1; i < nby; i++) {
+          const int y = (w.by + nby - i) % nby;
+          if (state[y] == kUntouched) {
+            w.by = y;
+            found = true;
+            break;
+          }
+        }
+      }
+      if (!found) {
+        live.erase(live.begin() + (ptrdiff_t)pick);
+        continue;
+      }
+      state[w.by] = kProcessing;
+      const bool use_upper = w.by > 0 && state[w.by - 1] == kDone;
+      decide_row(src, w.by, use_upper, w.lmx, w.lmy, bx1, bx2, by1, by2);
+      w.just_finished = w.by;
+    }
   }
   obx1 = bx1 == nbx ? -1 : bx1;
   oby1 = by1 == nby ? -1 : by1;
@@ -864,7 +928,11 @@ void FrameCodec::dec_begin(const uint8_t* p) {  // decodeBegin, screencap.h:295-
 }
 void FrameCodec::dec_count() {  // screencap.h:327-331
   if (++n_dec_ == kBlockEntries) {
-    rx_ = (uint32_t)in_[0] | ((uint32_t)in_[1] << 8) | ((uint32_t)in_[2] << 16) | ((uint32_t)in_[3] << 24);
+    // A frame of exactly k * 131072 entries has no block after this one (ransmt.h:83-90), and the reference loads the
+    // next state from the 4 bytes past the packet.  That state is never used; bytes past the end read as 0xFF, as in
+    // the product's decoder.
+    rx_ = 0;
+    for (int b = 0; b < 4; b++) rx_ |= (uint32_t)(in_ + b < in_end_ ? in_[b] : 0xFF) << (8 * b);
     in_ += 4;
     n_dec_ = 0;
   }
@@ -1086,6 +1154,7 @@ int FrameCodec::decode_inter(const uint8_t* src, uint8_t* dst) {  // DecompressP
 
 int FrameCodec::decompress(const uint8_t* src, int src_len, uint8_t* dst, int ftype) {  // :1522-1557
   dec_len_ = src_len;  // version 2 hands the packet length to its coder as it is (one more than what follows the header byte)
+  in_end_ = src + (src_len > 0 ? src_len : 0);
   if (W & 3) {
     int pad = stride_ - W * 3;
     for (int y = 0; y < H; y++) memset(dst + (size_t)y * stride_ + W * 3, 0, pad);
@@ -1134,6 +1203,7 @@ void ScreenCodec::create(int version) {  // CreateCodec, :1587-1617
   if (rgb32_ || rgb16_) buf_.assign((size_t)stride24 * H, 0);
   fc_ = new FrameCodec(p_, version);
   fc_->set_threads(threads_);
+  fc_->set_p_race(race_workers_, race_seed_);
 }
 
 void ScreenCodec::deinit() {  // :1619-1629

@@ -104,6 +104,12 @@ class FrameCodec {  // CScreenCapt<UseANS>
   int decompress(const uint8_t* src, int src_len, uint8_t* dst, int ftype);
   void set_loss(int loss);
   void set_threads(int n) { threads_ = n < 1 ? 1 : n; }
+  // Test support (not in the reference): decide P-frame blocks as `workers` workers of the reference's pool would under
+  // one interleaving drawn from `seed` (DecideBlockTypes, screencap.cpp:928-1087).  0 workers: the canonical order.
+  void set_p_race(int workers, uint64_t seed) {
+    race_workers_ = workers < 0 ? 0 : workers;
+    race_rng_ = seed;
+  }
   // Sharding support (not in the reference): the cross-GOP state a single stream would have where a shard starts -
   // whether a frame has been coded before (fn > 0, screencap.cpp:1504) and the flat-frame memory (last_was_flat /
   // last_flat_clr, :1490-1497, with prev holding that flat picture).
@@ -158,6 +164,9 @@ class FrameCodec {  // CScreenCapt<UseANS>
   bool is_flat(const uint8_t* src) const;
   void classify_intra(int worker, int y0, int ysize, const uint8_t* src);
   void decide_blocks(const uint8_t* src, int& bx1, int& bx2, int& by1, int& by2);
+  void decide_row(const uint8_t* src, int by, bool use_upper, int& lmx, int& lmy, int& bx1, int& bx2, int& by1, int& by2);
+  int race_workers_ = 0;  // 0: canonical single-worker P-frames; W: a seeded W-worker interleaving (set_p_race)
+  uint64_t race_rng_ = 0;
   bool find_motion(const uint8_t* src, int bi, int& lmx, int& lmy, int upper);
   bool same_rect(const uint8_t* src, int is, int ip, int wbytes, int h) const;
   int encode_intra(uint8_t* src, uint8_t* dst);
@@ -166,6 +175,7 @@ class FrameCodec {  // CScreenCapt<UseANS>
 
   // decoder
   const uint8_t* in_ = nullptr;
+  const uint8_t* in_end_ = nullptr;  // end of the packet: dec_count loads no byte past it
   uint32_t rx_ = 0;
   int n_dec_ = 0;
   int dec_len_ = 0;
@@ -196,6 +206,11 @@ class ScreenCodec {  // screencap.h:519-541, screencap.cpp:1560-1743
     threads_ = n;
     if (fc_) fc_->set_threads(n);
   }
+  void set_p_race(int workers, uint64_t seed) {
+    race_workers_ = workers;
+    race_seed_ = seed;
+    if (fc_) fc_->set_p_race(workers, seed);
+  }
   void seed_shard(uint32_t frames_before, bool last_flat, const uint8_t rgb[3]) {
     if (!fc_) create(p_.version == 3 ? 3 : p_.version == 2 ? 2 : 4);
     fc_->seed_shard(frames_before, last_flat, rgb);
@@ -212,6 +227,8 @@ class ScreenCodec {  // screencap.h:519-541, screencap.cpp:1560-1743
   FrameCodec* fc_ = nullptr;
   bool rgb32_ = false, rgb16_ = false, crashed_ = false;
   int threads_ = 1;
+  int race_workers_ = 0;
+  uint64_t race_seed_ = 0;
   uint32_t W = 0, H = 0, stride_ = 0, bpp_ = 0;
   int rs_ = 0, gs_ = 0, bs_ = 0, last_loss_ = 0;
   std::vector<uint8_t> buf_;

@@ -54,6 +54,7 @@ def lib():
         L.spo_time_stream2.argtypes = [C.POINTER(SpoParams), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
         L.spo_set_threads.argtypes = [C.c_void_p, C.c_int]
+        L.spo_set_p_race.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         L.spo_fnv1a.restype = C.c_uint64
         L.spo_fnv1a.argtypes = [C.c_void_p, C.c_uint64]
         _lib = L
@@ -99,6 +100,11 @@ class OracleCodec:
     def set_threads(self, n):
         lib().spo_set_threads(self.h_, n)
 
+    def set_p_race(self, workers, seed=0):
+        """P-frames as a `workers`-thread reference writes them under the thread timing drawn from `seed`
+        (DecideBlockTypes, screencap.cpp:928-1087); workers = 0: the canonical single-worker stream"""
+        lib().spo_set_p_race(self.h_, workers, seed)
+
     def seed_shard(self, frames_before, last_flat, rgb):
         lib().spo_seed_shard(self.h_, frames_before, 1 if last_flat else 0, rgb)
 
@@ -111,10 +117,13 @@ class OracleCodec:
         mv = np.ascontiguousarray(mv, dtype=np.int32).reshape(2, self.nblocks)
         assert lib().spo_import_mv_memory(self.h_, _ptr(mv[0]), _ptr(mv[1]), self.nblocks) == self.nblocks
 
-    def decompress(self, data, ftype, pitch=None):
+    def decompress(self, data, ftype, pitch=None, tail=b"\0" * 16):
+        """tail: bytes placed after the packet in the buffer the decoder reads (by default a 4-byte over-read guard,
+        SURVEY A.2).  With tail=b"" the buffer is a heap copy of exactly the packet, so a sanitizer build sees any
+        read past it."""
         pitch = self.pitch if pitch is None else pitch
         out = np.zeros(pitch * self.h, dtype=np.uint8)
-        buf = np.frombuffer(bytes(data) + b"\0" * 16, dtype=np.uint8)  # 4-byte over-read guard
+        buf = np.frombuffer(bytes(data) + bytes(tail), dtype=np.uint8).copy()
         r = lib().spo_decompress_frame(self.h_, _ptr(buf), len(data), _ptr(out), pitch, ftype)
         return r, out
 

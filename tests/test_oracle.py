@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import foreign_streams as foreign
 import oracle_api as O
 from screenpressor_amd.synth import DesktopSequence, pack24
 
@@ -336,3 +337,110 @@ def test_threaded_two_stage_shape_keeps_the_bytes():
     for b in b"abc":
         hv = ((hv ^ b) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
     assert O.fnv1a(b"abc") == hv
+
+
+# ---- streams the canonical encoder never writes (tests/foreign_streams.py) ----
+def _race_stream(frames, workers, seed, **kw):
+    h, w = frames[0].shape[:2]
+    enc = O.OracleCodec(w, h, 32, **kw)
+    enc.set_p_race(workers, seed)
+    return [enc.compress(f, key=(t == 0)) for t, f in enumerate(frames)]
+
+
+def _decodes_losslessly(packets, frames, **kw):
+    h, w = frames[0].shape[:2]
+    dec = O.OracleCodec(w, h, 32, **kw)
+    for (p, ft), f in zip(packets, frames):
+        r, out = dec.decompress(p, ft)
+        if r != 1 or not np.array_equal(out.reshape(h, w, 4), f):
+            return False
+    return True
+
+
+def _scroll_frames(n, w=160, h=96):
+    tex = np.random.default_rng(7).integers(0, 256, (h + 3 * n, w, 3), dtype=np.uint8)
+    out = []
+    for t in range(n):
+        f = np.full((h, w, 4), 255, np.uint8)
+        f[..., :3] = tex[3 * t:3 * t + h]
+        out.append(f)
+    return out
+
+
+def test_p_race_with_one_worker_is_the_canonical_stream():
+    """one worker claims every row in order with every row above Done: the canonical stream, whatever the seed"""
+    flat = np.full((96, 160, 4), 255, np.uint8)
+    flat[..., :3] = (9, 99, 199)
+    cases = [DesktopSequence(160, 120, seed=3).frames(6), DesktopSequence(100, 37, seed=4, noise_fraction=0.1).frames(5),
+             _scroll_frames(5), _scroll_frames(2) + [flat, flat] + _scroll_frames(3)]
+    for frames in cases:
+        can = _race_stream(frames, 0, 0)
+        for seed in (1, 2, 0xDEADBEEF):
+            assert _race_stream(frames, 1, seed) == can
+
+
+@pytest.mark.parametrize("workers", [2, 6, 16, 32])
+def test_p_race_changes_p_frames_and_every_stream_is_lossless(workers):
+    """W workers (the reference's pool on a W-core machine) choose other vectors or none: at least half of the P-frames of a
+    moving 320x240 desktop differ from the canonical stream over three timings, and each stream still decodes to its input"""
+    frames = DesktopSequence(320, 240, seed=3).frames(8)
+    can = _race_stream(frames, 0, 0)
+    differ = 0
+    for seed in (1, 2, 3):
+        got = _race_stream(frames, workers, seed)
+        assert got[0] == can[0]  # the key frame is not raced
+        differ += sum(a != b for a, b in zip(got[1:], can[1:]))
+        assert _decodes_losslessly(got, frames)
+    assert differ >= 3 * 7 // 2, differ
+
+
+def test_p_race_with_more_workers_than_block_rows():
+    """64x20 (2 block rows), W = 6: four workers get no band (squad.cpp:24-30) and only steal; row 1's vector depends on
+    whether row 0 was Done when it was claimed"""
+    frames = foreign.two_row_frames(6)
+    can = _race_stream(frames, 0, 0)
+    differ = 0
+    for seed in range(1, 5):
+        got = _race_stream(frames, 6, seed)
+        differ += sum(a != b for a, b in zip(got[1:], can[1:]))
+        assert _decodes_losslessly(got, frames)
+    assert differ >= 4 * 5 // 2, differ
+
+
+def _decode_exact_and_with_garbage(dec_factory, packets, frames):
+    """decode from a heap buffer of exactly each packet's length (a sanitizer build sees any read past it), then with
+    different garbage after the packet: the same pictures, and they are the input"""
+    outs = []
+    for tail in (b"", b"\xff" * 8, bytes(range(37, 45)), b"\0" * 3):
+        dec = dec_factory()
+        got = []
+        for (p, ft), f in zip(packets, frames):
+            r, out = dec.decompress(p, ft, tail=tail)
+            assert r == 1 and np.array_equal(out.reshape(f.shape), f)
+            got.append(out)
+        outs.append(got)
+    for got in outs[1:]:
+        assert all(np.array_equal(a, b) for a, b in zip(got, outs[0]))
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_key_frame_of_exactly_k_blocks(k):
+    """a key frame of exactly k * 131072 entries: no tail block, and the decoder's reload after the last block finds no bytes"""
+    f = foreign.exact_key_1() if k == 1 else foreign.exact_key_2()
+    h, w = f.shape[:2]
+    enc = O.OracleCodec(w, h, 32)
+    p, ft = enc.compress(f, key=True)
+    assert ft == 0 and len(enc.entries()) == k * foreign.BLOCK
+    _decode_exact_and_with_garbage(lambda: O.OracleCodec(w, h, 32), [(p, ft)], [f])
+
+
+def test_p_frame_of_exactly_one_block_and_the_frame_after_it():
+    frames = foreign.exact_p_pair()
+    h, w = frames[0].shape[:2]
+    enc = O.OracleCodec(w, h, 32)
+    packets = []
+    for t, f in enumerate(frames):
+        packets.append(enc.compress(f, key=(t == 0)))
+        if t == 1:
+            assert packets[1][1] == 1 and len(enc.entries()) == foreign.BLOCK
+    _decode_exact_and_with_garbage(lambda: O.OracleCodec(w, h, 32), packets, frames)
